@@ -2,7 +2,7 @@
 """Headline benchmark: boosting iterations/sec + AUC on synthetic Higgs-shape
 10M x 28 binary data, 255 bins, 63 leaves (BASELINE.json), HIP learner on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N>1 runs under torchrun, one process per GPU: the 10M training rows are split
 evenly across ranks (strong scaling: the job always trains on the same 10M x 28
@@ -10,7 +10,10 @@ dataset) and every tree is grown data-parallel with the smaller child's
 histogram all-reduced over RCCL. A "step" is one full boosting iteration
 (gradients, tree growth, score update). W untimed iterations, then exactly K
 timed iterations between barrier + device synchronisation on both sides; the
-max over ranks is reported. AUC is computed after timing on a held-out set.
+max over ranks is reported. A plain run does only that: set up, warm up, time the K
+steps, print the result line. `--dump-outputs DIR` also writes what the last timed step left
+behind (see _dump_outputs); `--full` adds the checks that take work of their own, today the
+AUC of the trained model on a held-out set (null in the result line of a plain run).
 """
 from __future__ import annotations
 
@@ -52,6 +55,10 @@ def main() -> int:
     ap.add_argument("--dp-host-transport", action="store_true",
                     help="N>1 ranks sharing one GPU: stage the data-parallel collectives through host "
                          "memory over gloo (multi-rank rehearsal; not a performance configuration)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the trained model's outputs to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks beyond the headline figure: AUC on a held-out set")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -146,8 +153,10 @@ def main() -> int:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(booster, args)
     auc = None
-    if rank == 0:
+    if rank == 0 and args.full:
         Xv, yv = make_higgs_like(args.valid_rows, seed=args.seed + 1000)
         pred = booster.predict(Xv)
         auc = _auc(yv, pred)
@@ -167,7 +176,7 @@ def main() -> int:
                             if args.num_leaves in BASELINE_IT_S and args.max_bin == 255 else None),
             "dtype": "fp32",  # fp32 (g, h); fixed-point histogram sums (gpu_use_dp: fp64)
             "data": "synthetic",
-            "auc": round(auc, 6),
+            "auc": round(auc, 6) if auc is not None else None,
             "config": {
                 "model": f"gbdt binary, {args.num_leaves} leaves, {args.max_bin} bins, lr 0.1"
                          + (", gpu_use_dp" if args.use_dp else "")
@@ -197,6 +206,23 @@ def main() -> int:
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+def _dump_outputs(booster, args, sample_rows: int = 200_000) -> None:
+    """What the timed path computed, as a caller of Booster.update() receives it: the model after
+    the last timed step. Written as the raw scores (float64) of the first `sample_rows` training
+    rows, which are regenerated from the seed and so identical from run to run, under the whole
+    model and under the trees of the last timed step alone. 2 x 1.6 MB at the default sizes."""
+    from lambdagap_amd.utils import make_higgs_like
+
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    Xs, _ = make_higgs_like(args.rows, seed=args.seed, start=0, stop=min(args.rows, sample_rows))
+    it = booster.current_iteration()
+    outputs = {"raw_score": booster.predict(Xs, raw_score=True)}
+    if it > 0:
+        outputs["last_step_raw_score"] = booster.predict(Xs, start_iteration=it - 1, num_iteration=1, raw_score=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def _spawn_ranks(n: int) -> int:

@@ -18,8 +18,8 @@ run() {  # run <name> <limit> <cmd...>
   tail -3 $OUT/$name.log | cut -c1-600 >> $OUT/steps.log
   [ $rc -eq 0 ] || exit $rc
 }
-run bench 300 python bench.py --gpus 1 --steps 20 --warmup 5
-run bench_1p25 300 python bench.py --rows 1250000 --steps 50 --warmup 5
+run bench 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full
+run bench_1p25 300 python bench.py --rows 1250000 --steps 50 --warmup 5 --full
 run prof 400 rocprofv3 --kernel-trace --stats -d $PWD/$OUT/prof -o run -- python3 bench.py --steps 20 --warmup 3
 python scripts/prof_summary.py $OUT/prof "Headline 10M x 28, 63 leaves" 23 > $OUT/prof_summary.md 2>&1; rm -rf $OUT/prof
 if [ "${2:-}" != "skip-tests" ]; then

@@ -13,7 +13,7 @@ run() {  # run <name> <limit> <cmd...>
 }
 run gputests 700 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread -p no:cacheprovider
 run smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
-run bench 300 python bench.py --steps 40 --warmup 3
+run bench 300 python bench.py --steps 40 --warmup 3 --full
 if [ "${PROF:-1}" = 1 ]; then
   run prof 400 rocprofv3 --kernel-trace --stats -d $PWD/$OUT/prof -o run -- python3 bench.py --steps 10 --warmup 2
   python scripts/prof_summary.py $OUT/prof "10M x 28, 63 leaves (bench.py --steps 10 --warmup 2)" 12 > $OUT/prof_summary.md 2>&1

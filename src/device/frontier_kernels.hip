@@ -3510,6 +3510,7 @@ __global__ __launch_bounds__(kFSelThreads) void k_f_select(FArgs a) {
 //  (sum all-reduce of the rows: exact integers, identical on every rank)
 //  k_f_vote_scan   the GLOBAL pass: each elected feature scanned from the summed rows with the
 //                  global leaf statistics and penalties, into the candidate table the select reads
+//  k_f_vote_xrng   extra trees: the feature streams advanced by the global pass's draws
 // Reference: voting_parallel_tree_learner.cpp:243-399 (FindBestSplits, GlobalVoting :150-181).
 constexpr int kVoteThreads = 256;
 
@@ -3715,6 +3716,50 @@ __device__ void FElectBody(const FArgs& a, int k, int q) {
   }
 }
 
+// Extra trees in the global pass: whether pair q's sibling elected feature f too
+__device__ __forceinline__ bool FVoteBothElected(const FArgs& a, int k, int q, int f) {
+  const int K = a.vote_k, other = q ^ 1;
+  bool both = false;
+  if (FPairChild(a, k, other) >= 0) {
+    const int* eo = a.velect + static_cast<size_t>(other) * (K + 1);
+    for (int i = 0; i < eo[0]; ++i) both = both || eo[1 + i] == f;
+  }
+  return both;
+}
+
+// the threshold that item (q, elected numerical feature f) draws from f's stream as the local pass
+// left it; `*x`: the stream's state after the draw
+__device__ __forceinline__ int FVoteScanDraw(const FArgs& a, int q, bool both, int f, const DevFeature& fi, unsigned* x) {
+  *x = a.xrng[f];
+  if (fi.num_bin - 2 <= 0) return 0;
+  if ((q & 1) == 1 && both) (void)LcgNext(x);
+  return RandNextInt(x, 0, fi.num_bin - 2);
+}
+
+// after k_f_vote_scan (extra trees only): one thread per (pair, elected slot). The item that drew
+// last from its feature's stream this round (the larger child's when both children elected the
+// feature, else the only one) repeats its draw and stores the stream's state: one thread per
+// feature reads and writes it.
+__global__ __launch_bounds__(64) void k_f_vote_xrng(FArgs a) {
+  const FState* stp = a.st;
+  if (stp->done) return;
+  const int K = a.vote_k, k = stp->k;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int q = i / K, j = i - q * K;
+  if ((q >> 1) >= k) return;
+  if (FPairChild(a, k, q) < 0) return;
+  const int* el = a.velect + static_cast<size_t>(q) * (K + 1);
+  if (j >= el[0]) return;
+  const int f = el[1 + j];
+  const DevFeature fi = a.feat[f];
+  if (fi.bin_type != 0) return;
+  const bool both = FVoteBothElected(a, k, q, f);
+  if ((q & 1) == 0 && both) return;
+  unsigned x;
+  (void)FVoteScanDraw(a, q, both, f, fi, &x);
+  a.xrng[f] = x;
+}
+
 // one wave per (pair, elected slot)
 __global__ __launch_bounds__(64) void k_f_vote_scan(FArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -3775,22 +3820,14 @@ __global__ __launch_bounds__(64) void k_f_vote_scan(FArgs a) {
   // extra trees (numerical data, one expansion per round): feature f's stream drew for both children
   // in the local pass; the global pass draws for the smaller child's elected features, then the
   // larger's (host FindBestSplitsFromHistograms order). Both children's items read the stream as
-  // the local pass left it: the larger's item replays the smaller's draw first when f was elected
-  // for both, and only the item that draws last stores the state back.
+  // the local pass left it:
+  // the larger's item replays the smaller's draw first when f was elected for both. No item
+  // stores the state here (the two children's items run in no order, and a store by one would
+  // race the other's read): k_f_vote_xrng, next on the stream, advances the streams.
   int rt = 0;
   if (a.xrng != nullptr && fi.bin_type == 0) {
-    const int sel = q & 1, other = q ^ 1;
-    bool both = false;
-    if (FPairChild(a, k, other) >= 0) {
-      const int* eo = a.velect + static_cast<size_t>(other) * (K + 1);
-      for (int i = 0; i < eo[0]; ++i) both = both || eo[1 + i] == f;
-    }
-    unsigned x = a.xrng[f];
-    if (fi.num_bin - 2 > 0) {
-      if (sel == 1 && both) (void)LcgNext(&x);
-      rt = RandNextInt(&x, 0, fi.num_bin - 2);
-    }
-    if (lane == 0 && (sel == 1 || !both)) a.xrng[f] = x;
+    unsigned x;
+    rt = FVoteScanDraw(a, q, FVoteBothElected(a, k, q, f), f, fi, &x);
   }
   bool spl;
   if (fi.bin_type == 0) {
@@ -4204,6 +4241,10 @@ void LaunchFrontierElect(const FArgs& a, hipStream_t s) {
 void LaunchFrontierVoteScan(const FArgs& a, size_t lds, hipStream_t s) {
   k_f_vote_scan<<<2 * a.kmax * a.vote_k, 64, lds, s>>>(a);
   HIP_CHECK(hipGetLastError());
+  if (a.xrng != nullptr) {
+    k_f_vote_xrng<<<(2 * a.kmax * a.vote_k + 63) / 64, 64, 0, s>>>(a);
+    HIP_CHECK(hipGetLastError());
+  }
 }
 
 void LaunchFrontierPairBest(const FArgs& a, hipStream_t s) {

@@ -2101,9 +2101,7 @@ def test_bagging_by_query_in_lambdarank(lgb):
     """test_bagging_by_query_in_lambdarank (reference examples/lambdarank data)."""
     import os
     from sklearn.datasets import load_svmlight_file
-    d = os.path.join(os.path.dirname(__file__), "data", "examples", "lambdarank")
-    if not os.path.exists(os.path.join(d, "rank.train")):
-        d = "/root/reference/examples/lambdarank"
+    d = os.path.join(os.path.dirname(__file__), "data")
     X_tr, y_tr = load_svmlight_file(os.path.join(d, "rank.train"))
     X_te, y_te = load_svmlight_file(os.path.join(d, "rank.test"))
     q_tr = np.loadtxt(os.path.join(d, "rank.train.query"))
