@@ -30,21 +30,8 @@ bool CommActive();
 
 // Single-process HIP tree learner (device_type=gpu|cuda) and its data-parallel
 // variant (tree_learner=data|voting|feature with an RCCL communicator).
+// TreeLearner::Create routes here what the engine plan (src/device/engine_plan.h) serves on the device.
 std::unique_ptr<TreeLearner> CreateDeviceTreeLearner(const Config* config, const std::string& parallel_mode);
-// Whether the device learner's frontier engine can grow `config`'s trees on `train` (learner
-// type, sampling options and the engine's fixed LDS / node-capacity shape). The options only
-// the frontier implements on the device (forced splits, CEGB feature penalties) route to the
-// host split policy when it cannot.
-bool FrontierServes(const Config* config, const Dataset* train, const std::string& learner_type);
-// The same for feature_fraction_bynode under interaction constraints: the frontier's select
-// draws each node's mask over the features its constraints allow (serial learner only).
-bool FrontierServesByNode(const Config* config, const Dataset* train, const std::string& learner_type);
-// intermediate monotone constraints in the serial frontier's select (FArgs::mono_inter): no by-node
-// sampling, extra trees, forced splits or CEGB, and the select's extra LDS fits
-bool FrontierServesMonoInter(const Config* config, const Dataset* train, const std::string& learner_type);
-// Whether the device learner fits linear_tree leaves itself (fp64 MFMA Gram systems): serial
-// learner, float gradients, raw values kept, and at most 30 branch features per leaf.
-bool LinearOnDevice(const Config* config, const Dataset* train, const std::string& learner_type);
 
 // GPU histogram engine for the host learners (the reference's GPUTreeLearner
 // split, src/treelearner/gpu_tree_learner.cpp: histograms on the device, split

@@ -97,6 +97,7 @@
 #include "device/policy_scan.h"
 #include "device/traverse_kernels.h"
 #include "device/sample_kernels.h"
+#include "device/engine_plan.h"
 #include "device/seq_kernels.h"
 #include "device/split_scan.h"
 #include "device/tree_kernels.h"
@@ -177,48 +178,12 @@ class PinnedBuf {
   size_t n_ = 0;
 };
 
-// Parallel modes of the device learner (tree_learner=serial|data|feature|voting).
-enum class DevParallel { kSerial, kData, kFeature, kVoting };
-
-// Computed-node capacity of one frontier tree: every committed node (2 L - 1) plus room for
-// speculation (8 L + 2 kmax, fewer when the per-node fp64 histograms would exceed ~8 GiB).
-int FrontierCapacityFor(int L, int TB) {
-  const long long lo = 4LL * L + 2 * kFrontierKmax, hi = 8LL * L + 2 * kFrontierKmax;
-  const long long slot_bytes = 16LL * std::max(TB, 1);
-  const long long fit = (8LL << 30) / slot_bytes;
-  const long long c = std::max(lo, std::min({hi, fit, static_cast<long long>(kFrontierMaxNodes)}));
-  return static_cast<int>(c);
-}
-
-// LDS of the frontier's k_f_scan: two full fp64 (g, h) histograms of the widest feature plus
-// the categorical sort arrays (index, ctr) of both scanning waves.
-size_t FrontierScanLds(int max_bin, int max_cat_bin) {
-  int cat_p2 = 1;
-  while (cat_p2 < max_cat_bin) cat_p2 <<= 1;
-  return static_cast<size_t>(max_bin) * 4 * sizeof(double) + static_cast<size_t>(cat_p2) * 2 * (sizeof(int) + sizeof(double));
-}
-
-// Whether a tree of L leaves over TB total bins / F features fits the frontier engine's fixed
-// resources: the select's LDS image of the computed nodes (plus the CEGB used flags), the node
-// capacity, and the scan's LDS. LGAP_FRONTIER=0 forces the sequential chain (A/B runs). The
-// learner factory routes with the same predicate (FrontierServes), so a configuration the
-// frontier cannot hold takes the host split policy instead of failing at allocation.
-bool FrontierShapeFits(int L, int TB, int F, int max_bin, int max_cat_bin, bool cegb_raw, bool mono_inter) {
-  const char* e = std::getenv("LGAP_FRONTIER");
-  if (e != nullptr && e[0] == '0') return false;
-  const int C = FrontierCapacityFor(std::max(2, L), TB);
-  if (C > kFrontierMaxNodes || F <= 0) return false;
-  if (FrontierScanLds(max_bin, max_cat_bin) > 150 * 1024) return false;
-  // (raw candidates: the CEGB used-feature flags and the by-node draws' scratch, F bytes each)
-  return FrontierSelectLds(C, std::max(2, L)) + (cegb_raw ? 2 * (F + 16) : 0) +
-             (mono_inter ? FrontierSelectMonoLds(C, std::max(2, L), F) : 0) <=
-         150 * 1024;
-}
-
 class DeviceTreeLearner : public TreeLearner {
  public:
-  DeviceTreeLearner(const Config* config, DevParallel mode)
-      : config_(config), mode_(mode), data_parallel_(mode == DevParallel::kData) {}
+  // routed: made by TreeLearner::Create, whose engine plan sent the configuration here (the
+  // histogram backend of the host policy and the kernel test hooks make theirs directly)
+  DeviceTreeLearner(const Config* config, const std::string& learner_type, bool routed = false)
+      : config_(config), learner_type_(learner_type), routed_(routed) {}
 
   ~DeviceTreeLearner() override {
     if (fres_host_) (void)hipHostFree(fres_host_);
@@ -247,25 +212,13 @@ class DeviceTreeLearner : public TreeLearner {
     width_ = train->bin_width();
     stride_dw_ = train->row_stride() / 4;
     tstride_dw_ = stride_dw_;
-    const bool parallel = mode_ != DevParallel::kSerial;
-    if (parallel && !CommActive() && !HostStagedDP() && Network::num_machines() > 1) {
+    if (learner_type_ != "serial" && !CommActive() && !HostStagedDP() && Network::num_machines() > 1) {
       Log::Fatal("Parallel HIP training needs an RCCL communicator (LGBM_DeviceCommInit)");
     }
-    // LGAP_FORCE_DEVICE_DP=1 (or =voting) routes a single-rank run through the data-parallel (or
-    // voting-parallel) path on a one-rank communicator: the configuration sets tree_learner to
-    // serial for one machine, as the reference does, so a 1-GPU box needs this to run either path.
-    const char* force_dp = std::getenv("LGAP_FORCE_DEVICE_DP");
-    const bool force_vote = force_dp != nullptr && std::strcmp(force_dp, "voting") == 0;
-    const bool forced = CommExists() && force_dp != nullptr && (force_dp[0] == '1' || force_vote);
-    if (forced && mode_ == DevParallel::kSerial) {
-      mode_ = force_vote ? DevParallel::kVoting : DevParallel::kData;
-      data_parallel_ = !force_vote;
-    }
-    const bool multi = CommActive() || HostStagedDP() || forced;
-    // voting: a one-rank communicator also runs the voting path (single-GPU rehearsal)
-    voting_ = mode_ == DevParallel::kVoting && (multi || CommExists());
-    owner_scan_ = (mode_ == DevParallel::kData || mode_ == DevParallel::kFeature) && multi;
-    distributed_ = (owner_scan_ && data_parallel_) || voting_;
+    // the parallel mode and its flags, which the upload and SetupOwnership below read (ResetConfig
+    // plans again, for the engine)
+    plan_in_ = PlanInputs();
+    Replan();
     device_id_ = CommExists() ? CommDevice() : std::max(0, config_->gpu_device_id);
     HIP_CHECK(hipSetDevice(device_id_));
     hipDeviceProp_t prop;
@@ -297,15 +250,15 @@ class DeviceTreeLearner : public TreeLearner {
     ResetConfig(config_);
     SetupTransport();
     Log::Info("HIP tree learner on %s: %d rows, %d features, %d groups, %d bins%s", device_name_.c_str(), N_, F_, G_,
-              TB_, (owner_scan_ || voting_) ? (" (" + ParallelDesc() + ")").c_str() : "");
+              TB_, (plan_.owner_scan || plan_.voting) ? (" (" + ParallelDesc() + ")").c_str() : "");
   }
 
   // Feature-group ownership of the owner-computes modes: contiguous group ranges with
   // ~equal bins per rank (the host DataParallelTreeLearner's assignment), so rank r's
   // block of the histogram is the contiguous bin range [bin_lo[r], bin_lo[r + 1]).
   void SetupOwnership() {
-    P_ = (owner_scan_ || voting_) ? DpSize() : 1;
-    rank_ = (owner_scan_ || voting_) ? DpRank() : 0;
+    P_ = (plan_.owner_scan || plan_.voting) ? DpSize() : 1;
+    rank_ = (plan_.owner_scan || plan_.voting) ? DpRank() : 0;
     h_bin_lo_.assign(P_ + 1, TB_);
     std::vector<int> owner(G_);
     for (int g = 0; g < G_; ++g) {
@@ -330,19 +283,19 @@ class DeviceTreeLearner : public TreeLearner {
     std::vector<int> cnt(P_, 0);
     h_own_feat_.clear();
     for (int f = 0; f < F_; ++f) {
-      const int r = owner_scan_ ? owner[data_->feature(f).group] : 0;
+      const int r = plan_.owner_scan ? owner[data_->feature(f).group] : 0;
       ++cnt[r];
       if (r == rank_) h_own_feat_.push_back(f);
     }
     Fmax_ = 1;
     for (int r = 0; r < P_; ++r) Fmax_ = std::max(Fmax_, cnt[r]);
-    if (!owner_scan_) Fmax_ = std::max(1, F_);
+    if (!plan_.owner_scan) Fmax_ = std::max(1, F_);
     h_own_feat_.resize(Fmax_, -1);
     const size_t kb = Round256(2 * static_cast<size_t>(Fmax_) * sizeof(SplitKey));
     const size_t ib = Round256(2 * static_cast<size_t>(Fmax_) * sizeof(SplitInfo));
     cand_key_bytes_ = static_cast<int>(kb);
     cand_stride_ = static_cast<int>(kb + ib);
-    if (voting_) SetupVoting();
+    if (plan_.voting) SetupVoting();
   }
 
   static size_t Round256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
@@ -369,30 +322,24 @@ class DeviceTreeLearner : public TreeLearner {
   // xGMI in-kernel exchange when every rank maps every peer and the self-test passes, else
   // collectives) | xgmi | collective | allreduce.
   void SetupTransport() {
-    if (!owner_scan_ && !voting_) return;
-    const char* e = std::getenv("LGAP_DP_TRANSPORT");
-    const std::string want = e ? e : "auto";
-    if (want != "auto" && want != "xgmi" && want != "collective" && want != "allreduce") {
-      Log::Fatal("LGAP_DP_TRANSPORT=%s: expected auto|xgmi|collective|allreduce", want.c_str());
+    if (!plan_.owner_scan && !plan_.voting) return;
+    const RoutingEnv& env = plan_in_.env;
+    if (env.dp_transport == DpTransport::kOther) {
+      Log::Fatal("LGAP_DP_TRANSPORT=%s: expected auto|xgmi|collective|allreduce", env.dp_transport_text.c_str());
     }
-    // the distributed frontier engine: the in-kernel xGMI exchange (auto / xgmi) where its
-    // exchanges are the owner histogram chunks and the per-child bests (owner-computes data
-    // parallel, feature parallel); collectives otherwise (collective, allreduce, voting, raw
-    // per-feature candidates)
-    if (frontier_) {
-      if ((want == "auto" || want == "xgmi") && (fowner_ || ffeature_ || fvoting_) && P_ <= kMaxXRanks) {
-        SetupFrontierXgmi(want == "xgmi");
-      }
-      else if (want == "xgmi") Log::Warning("xGMI transport: this frontier configuration exchanges through collectives");
-      // (TreeLearner::Create routes voting + extra trees over collectives to the host policy: the
-      // frontier's global-pass redraws are verified over the in-kernel exchange only)
-      if (fvoting_ && config_->extra_trees && !FrontierXg()) {
-        Log::Fatal("voting-parallel with extra_trees on the device needs the xGMI transport (set up failed)");
-      }
-      return;
+    // the plan asks for the in-kernel xGMI exchange (auto / xgmi) where the frontier's exchanges
+    // are the owner histogram chunks, the per-child bests or the votes; collectives otherwise
+    // (collective, allreduce, raw per-feature candidates, the sequential chain)
+    if (plan_.try_xgmi) {
+      SetupFrontierXgmi(plan_.xgmi_required);
+    } else if (env.dp_transport == DpTransport::kXgmi) {
+      Log::Warning(frontier_ ? "xGMI transport: this frontier configuration exchanges through collectives"
+                             : "xGMI transport: the sequential chain exchanges through collectives");
     }
-    // the sequential chain (configurations the frontier does not hold) exchanges through collectives
-    if (want == "xgmi") Log::Warning("xGMI transport: the sequential chain exchanges through collectives");
+    // KNOWN: fatal at run time where the host policy could serve (engine_plan.cpp)
+    if (plan_.xgmi_needed && !FrontierXg()) {
+      Log::Fatal("voting-parallel with extra_trees on the device needs the xGMI transport (set up failed)");
+    }
   }
 
   // The distributed frontier's in-kernel exchange (FArgs::xg): one uncached exchange buffer per
@@ -483,8 +430,8 @@ class DeviceTreeLearner : public TreeLearner {
   }
 
   std::string ParallelDesc() const {
-    std::string m = mode_ == DevParallel::kFeature ? "feature-parallel"
-                                                   : (voting_ ? "voting-parallel" : "data-parallel");
+    std::string m = plan_.mode == ParallelMode::kFeature ? "feature-parallel"
+                                                   : (plan_.voting ? "voting-parallel" : "data-parallel");
     m += ", " + std::to_string(P_) + " ranks, ";
     if (frontier_) {
       const std::string via = HostStagedDP() ? "host-staged collectives" : "RCCL";
@@ -503,8 +450,24 @@ class DeviceTreeLearner : public TreeLearner {
     config_ = config;
     col_sampler_.Init(data_, config_);
     L_ = std::max(2, config_->num_leaves);
+    Replan();
     AllocState();
     InvalidateGraph();
+  }
+
+  // The engine plan of the current configuration (engine_plan.h), and the flags read all over the
+  // learner. The parallel mode is Init's (SetupOwnership sizes the exchanges for it), so a later
+  // plan keeps Init's LGAP_FORCE_DEVICE_DP.
+  void Replan() {
+    const bool first = plan_in_.config == nullptr;
+    const ForceDP force_dp = plan_in_.env.force_dp;
+    plan_in_ = GatherPlanInputs(learner_type_, config_->linear_tree, config_, data_);
+    if (!first) plan_in_.env.force_dp = force_dp;
+    plan_ = PlanEngine(plan_in_);
+    frontier_ = plan_.frontier != FrontierMode::kNone;
+    fowner_ = plan_.frontier == FrontierMode::kDataOwner;
+    ffeature_ = plan_.frontier == FrontierMode::kFeature;
+    fvoting_ = plan_.frontier == FrontierMode::kVoting;
   }
 
   void SetBaggingData(const data_size_t* used, data_size_t n) override {
@@ -1611,7 +1574,7 @@ class DeviceTreeLearner : public TreeLearner {
     tp->root_count = use_bag_ ? bag_cnt_ : N_;
     tp->cls = class_id;
     int gcount = tp->root_count;
-    if (distributed_) {
+    if (plan_.distributed) {
       // the global root count changes only with the bag: one host collective per new bag
       if (gcount != cached_gcount_local_) {
         cached_gcount_local_ = gcount;
@@ -1633,8 +1596,8 @@ class DeviceTreeLearner : public TreeLearner {
     for (int f = 0; f < F_; ++f) um[f] = used[f] ? 1 : 0;
     HIP_CHECK(hipMemcpyAsync(used_bytree_.get(), um, F_, hipMemcpyHostToDevice, stream_));
     Random byn_state;
-    const bool byn_dev = use_bynode_ && frontier_ && ByNodeOnDevice();
-    if (use_bynode_ && !frontier_ && ByNodeOnDevice()) {
+    const bool byn_dev = frontier_ && plan_.bynode_on_device;
+    if (!frontier_ && plan_.bynode_on_device) {
       Log::Fatal("feature_fraction_bynode with interaction constraints needs the frontier engine (shape / node capacity)");
     }
     if (use_bynode_) {
@@ -1723,97 +1686,29 @@ class DeviceTreeLearner : public TreeLearner {
 
   // ---- frontier tree growth (frontier.h): batched rounds, replayed best-first order
 
-  // The frontier engine covers the single-device learner; bynode sampling and extra-trees
-  // draw per split in sequential order, the global-memory scan has no frontier variant, and
-  // the computed-node image of the select must fit its LDS. LGAP_FRONTIER=0 forces the
-  // sequential chain (A/B runs).
-  bool FrontierEligible() const {
-    if (!FrontierSerial() && !FrontierDP() && !FrontierVoting() && !FrontierFeature()) return false;
-    // extra trees: the single-device frontier and the voting frontier on numerical data (one
-    // expansion per round: FArgs::xrng; the global pass redraws in the host's order, k_f_vote_scan)
-    if (config_->extra_trees && !FrontierSerial() && !(FrontierVoting() && !has_cat_)) return false;
-    // by-node sampling: the single-device frontier (masks in the host's draw order, FArgs::bynode;
-    // under interaction constraints drawn in the select, FArgs::byn_draw)
-    if (use_bynode_ && !FrontierSerial()) return false;
-    if (MonoInter() && (!FrontierSerial() || RawCands() || config_->extra_trees || fnum_forced_ > 0 ||
-                        !config_->forcedsplits_filename.empty()))
-      return false;
-    return FrontierShapeFits(L_, TB_, F_, max_bin_, max_cat_bin_, RawCands(), MonoInter());
-  }
-  // per-node raw candidates of every feature (FArgs::cegb_raw): CEGB feature penalties, and
-  // by-node sampling (a node is scored once its mask is known)
-  bool RawCands() const { return CegbRaw() || use_bynode_; }
-  // intermediate monotone constraints in the frontier select (FArgs::mono_inter; the serial
-  // frontier only: TreeLearner::Create routes the other learners to the host policy)
-  bool MonoInter() const {
-    return !config_->monotone_constraints.empty() && config_->monotone_constraints_method == "intermediate";
-  }
-  // by-node masks drawn in the select: each node's pool follows its interaction constraints
-  bool ByNodeOnDevice() const { return use_bynode_ && !config_->interaction_constraints_vector.empty(); }
-  // CEGB feature penalties in the frontier select: coupled (FArgs::cegb_coupled: refunds on a
-  // feature's first use) and lazy (FArgs::cegb_lazy: per-row marks, unmarked-row counts per
-  // node). Either makes the scans publish raw gains (FArgs::cegb_raw).
-  bool CegbCoupled() const { return !config_->cegb_penalty_feature_coupled.empty(); }
-  bool CegbLazy() const { return !config_->cegb_penalty_feature_lazy.empty(); }
-  bool CegbRaw() const { return CegbCoupled() || CegbLazy(); }
-  bool FrontierSerial() const {
-    return mode_ == DevParallel::kSerial && !owner_scan_ && !voting_ && !distributed_;
-  }
+  // Which configurations grow on the frontier, and with which exchange, is the engine plan's
+  // decision (engine_plan.cpp: plan_.frontier, mirrored by frontier_ / fowner_ / ffeature_ /
+  // fvoting_; its flags raw_cands -> FArgs::cegb_raw, mono_inter, bynode_on_device -> byn_draw).
+  // Data parallel: every rank partitions / builds histograms of its own rows; every rank selects
+  // redundantly from identical candidates, so all ranks grow the same tree. Children's counts come
+  // from the summed histograms (the split record), row ranges from the local partition. Per round,
+  // either one exact integer all-reduce of the fixed-point accumulators (every rank scans every
+  // feature; reference data_parallel_tree_learner.cpp:148-297), or owner-computes rounds (fowner_,
+  // the default): the accumulators are REDUCE-SCATTERED by feature-group ownership (SetupOwnership),
+  // so each rank receives only the summed bins of its own features (half the bytes) and scans only
+  // those (1/P of the work); each child's best over the owned features is gathered and the best
+  // over ranks becomes its candidate (k_f_pair_best, then the select's phase A; reference :284-297,
+  // :305-450). Over the in-kernel xGMI transport (FrontierXg) or RCCL / the host-staged collectives.
+  // Voting parallel (fvoting_, PV-Tree per round): the local pass of every expansion's children,
+  // one all-gather of the round's top-k vote records, the election, one exact integer all-reduce of
+  // only the elected features' rows, and the global pass over them; over xGMI the records and rows
+  // are pushed in-kernel. Reference: voting_parallel_tree_learner.cpp:243-399.
+  // Feature parallel (ffeature_): every rank holds all rows and grows the same partition and
+  // histograms; the scans cover this rank's features, each child's best is exchanged (pushed over
+  // xGMI, or all-gathered). Reference: feature_parallel_tree_learner.cpp:23-80.
+
   // the frontier's exchanges run in-kernel over xGMI (SetupFrontierXgmi; FArgs::xg)
   bool FrontierXg() const { return fxg_ && frontier_ && (fowner_ || ffeature_ || fvoting_); }
-  // Data-parallel frontier: every rank partitions / builds histograms of its own rows, the
-  // round's fixed-point accumulators are summed over ranks (one exact integer all-reduce per
-  // round, RCCL or the host-staged rehearsal transport), and every rank scans and selects
-  // redundantly: the select is deterministic in the summed histograms, so all ranks grow the
-  // same tree with no further exchange. Children's counts come from the summed histograms
-  // (the split record), row ranges from the local partition. LGAP_FRONTIER_DP=0: the
-  // sequential owner-scan chain instead. Reference: data_parallel_tree_learner.cpp:148-297.
-  // The exchanges: the owner-computes rounds below (FrontierOwner) over the in-kernel xGMI
-  // transport (FrontierXg, the default where every rank maps every peer) or RCCL / the host-staged
-  // rehearsal collectives; the per-round all-reduce for configurations that need every feature.
-  bool FrontierDP() const {
-    const char* e = std::getenv("LGAP_FRONTIER_DP");
-    if (e != nullptr && e[0] == '0') return false;
-    return mode_ == DevParallel::kData && data_parallel_ && owner_scan_ && distributed_ && !voting_ &&
-           (CommExists() || HostStagedDP());
-  }
-  // Owner-computes data-parallel rounds (the default data-parallel frontier): the round's
-  // fixed-point accumulators are REDUCE-SCATTERED by feature-group ownership (SetupOwnership:
-  // contiguous, bin-balanced group ranges), so each rank receives only the summed bins of its own
-  // features (half the bytes of the all-reduce) and scans only those (1/P of the scan work); each
-  // child's best over the owned features is all-gathered and the best over ranks becomes the
-  // child's candidate (the feature-parallel exchange: k_f_pair_best, then the select's phase A); every rank
-  // then selects redundantly from identical candidates. Reference:
-  // data_parallel_tree_learner.cpp:284-297 (ReduceScatter of the smaller leaf's histograms by
-  // feature ownership), :305-450 (owner scans, SyncUpGlobalBestSplit). Raw per-feature candidates
-  // (CEGB penalties, by-node sampling) and forced splits need every feature's scan on every rank:
-  // they keep the all-reduce, as does LGAP_DP_TRANSPORT=allreduce (A/B).
-  bool FrontierOwner() const {
-    if (!FrontierDP() || RawCands() || !config_->forcedsplits_filename.empty() || config_->extra_trees) return false;
-    const char* t = std::getenv("LGAP_DP_TRANSPORT");
-    return !(t != nullptr && std::strcmp(t, "allreduce") == 0);
-  }
-  // Voting-parallel frontier (PV-Tree per round): the local pass of every expansion's children,
-  // one all-gather of the round's top-k vote records, the election, one exact integer
-  // all-reduce of only the elected features' rows, and the global pass over them; every rank
-  // then selects redundantly, as the data-parallel frontier does. Over xGMI the records and the
-  // elected rows are pushed in-kernel (FArgs::xg). Reference: voting_parallel_tree_learner.cpp:243-399.
-  bool FrontierVoting() const {
-    return mode_ == DevParallel::kVoting && voting_ && distributed_ && (CommExists() || HostStagedDP());
-  }
-  // Feature-parallel frontier: every rank holds all rows and grows the same partition and
-  // histograms; the scans cover this rank's features (the groups it owns), each child's best is
-  // exchanged (pushed over xGMI, or all-gathered) and the best over ranks is the child's candidate.
-  // Reference: feature_parallel_tree_learner.cpp:23-80.
-  bool FrontierFeature() const {
-    return mode_ == DevParallel::kFeature && owner_scan_ && !distributed_ && (CommExists() || HostStagedDP());
-  }
-  int FrontierKmax() const {
-    return std::max(1, std::min(kFrontierKmax, L_ - 1));
-  }
-  // computed nodes of one tree: every committed node (2 L - 1) plus room for speculation
-  // (8 L + 2 kmax, fewer when the per-node fp64 histograms would exceed ~8 GiB)
-  int FrontierCapacity() const { return FrontierCapacityFor(L_, TB_); }
 
   // forcedsplits_filename -> the FForced list the frontier select applies first (the host
   // learner's order and skips: learner/forced_splits.h)
@@ -1847,27 +1742,19 @@ class DeviceTreeLearner : public TreeLearner {
   }
 
   void AllocFrontier() {
-    frontier_ = FrontierEligible();
-    if (!frontier_ && !config_->forcedsplits_filename.empty()) {
-      // (TreeLearner::Create routes these by FrontierServes: reaching here is a routing bug)
-      Log::Fatal("forced splits on the device need the frontier engine (serial learner, no "
-                 "feature_fraction_bynode / extra_trees, frontier LDS shape)");
-    }
-    if (!frontier_ && config_->interaction_constraints_vector.size() > 64) {
-      // (TreeLearner::Create routes these by FrontierServes: reaching here is a routing bug)
-      Log::Fatal("more than 64 interaction constraint sets on the device need the frontier engine");
-    }
-    if (!frontier_ && MonoInter()) {
-      // (TreeLearner::Create routes these by FrontierServesMonoInter: reaching here is a routing bug)
-      Log::Fatal("intermediate monotone constraints on the device need the serial frontier engine");
-    }
-    if (!frontier_ && CegbRaw()) {
-      Log::Fatal("cegb_penalty_feature_coupled / _lazy on the device need the frontier engine (serial learner, "
-                 "no feature_fraction_bynode / extra_trees, frontier LDS shape)");
+    // What only the frontier's select implements (forced splits, more than 64 constraint sets,
+    // intermediate monotone constraints, CEGB feature penalties) and what the host policy serves
+    // never belong here: the factory plans with the same function, so this is a routing bug.
+    const bool needs_frontier = !config_->forcedsplits_filename.empty() || plan_.mono_inter || plan_.cegb_coupled ||
+                                plan_.cegb_lazy || config_->interaction_constraints_vector.size() > 64;
+    if ((routed_ && plan_.engine == Engine::kHostPolicy) || (!frontier_ && needs_frontier)) {
+      Log::Fatal("engine routing: the factory's plan and the learner's plan name different engines (factory: %s; "
+                 "learner: %s%s%s)", needs_frontier ? "frontier engine" : "device learner", EngineName(plan_.engine),
+                 plan_.host_reason ? ", " : "", plan_.host_reason ? plan_.host_reason : "");
     }
     if (!frontier_) return;
-    fkmax_ = FrontierKmax();
-    fC_ = FrontierCapacity();
+    fkmax_ = std::max(1, std::min(kFrontierKmax, L_ - 1));
+    fC_ = FrontierCapacityFor(L_, TB_);
     const size_t C = fC_, K = fkmax_, F = std::max(F_, 1);
     ArenaLayout lay;
     const size_t o_st = lay.Add<FState>(1), o_nodes = lay.Add<FNode>(C), o_exps = lay.Add<FExp>(K),
@@ -1876,7 +1763,7 @@ class DeviceTreeLearner : public TreeLearner {
                  o_spl = lay.Add<uint8_t>(C * F), o_ic = lay.Add<unsigned long long>(C * kFrontierIcWords), o_nst = lay.Add<uint8_t>(C),
                  o_lcid = lay.Add<int>(L_), o_ckey = lay.Add<SplitKey>(K * 2 * F), o_cinfo = lay.Add<SplitInfo>(K * 2 * F),
                  o_fbest = lay.Add<SplitInfo>(C), o_fkey = lay.Add<SplitKey>(C),
-                 o_cbnd = lay.Add<LeafBounds>(MonoInter() ? C : 1), o_sal = lay.Add<int>(C);
+                 o_cbnd = lay.Add<LeafBounds>(plan_.mono_inter ? C : 1), o_sal = lay.Add<int>(C);
     farena_.Resize(lay.bytes());
     farena_.Zero(stream_);
     char* b = farena_.get();
@@ -1897,16 +1784,16 @@ class DeviceTreeLearner : public TreeLearner {
     fcinfo_ = reinterpret_cast<SplitInfo*>(b + o_cinfo);
     ffbest_ = reinterpret_cast<SplitInfo*>(b + o_fbest);
     ffkey_ = reinterpret_cast<SplitKey*>(b + o_fkey);
-    fcbnd_ = MonoInter() ? reinterpret_cast<LeafBounds*>(b + o_cbnd) : nullptr;
+    fcbnd_ = plan_.mono_inter ? reinterpret_cast<LeafBounds*>(b + o_cbnd) : nullptr;
     fsal_ = reinterpret_cast<int*>(b + o_sal);
     UploadForcedSplits();
-    if (RawCands()) {
+    if (plan_.raw_cands) {
       fnkey_.Resize(C * F);
       fninfo_.Resize(C * F);
       fnuep_.Resize(C);
       fnuep_.Zero(stream_);
     }
-    if (CegbCoupled()) {
+    if (plan_.cegb_coupled) {
       // tradeoff x coupled penalty per inner feature; used flags and the event count persist
       // over the trees of this training set (host CegbPenalty::Init)
       const auto& cp = config_->cegb_penalty_feature_coupled;
@@ -1926,7 +1813,7 @@ class DeviceTreeLearner : public TreeLearner {
         cegb_epoch_.Zero(stream_);
       }
     }
-    if (CegbLazy()) {
+    if (plan_.cegb_lazy) {
       // tradeoff x lazy penalty per inner feature; per-row marks persist over the trees
       const auto& lp = config_->cegb_penalty_feature_lazy;
       if (static_cast<int>(lp.size()) != data_->num_total_features()) {
@@ -1961,7 +1848,7 @@ class DeviceTreeLearner : public TreeLearner {
     // global row count (data parallel: the packed quantized accumulators must hold every
     // rank's level sums)
     fglobal_rows_ = static_cast<double>(N_);
-    if (distributed_) {
+    if (plan_.distributed) {
       DevBuf<double> gr(1);
       const double nloc = static_cast<double>(N_);
       gr.Upload(&nloc, 1, stream_);
@@ -1980,8 +1867,6 @@ class DeviceTreeLearner : public TreeLearner {
 
       if (num_tiles_ > 256) Log::Fatal("frontier histograms: %d LDS tiles (at most 256)", num_tiles_);
     }
-    ffeature_ = FrontierFeature();
-    fowner_ = FrontierOwner();
     if (ffeature_ || fowner_) {
       std::vector<uint8_t> own(F_, 0);
       std::vector<int> list;
@@ -2005,14 +1890,13 @@ class DeviceTreeLearner : public TreeLearner {
       facc_.Zero(stream_);
       facc_recv_.Resize(static_cast<size_t>(K) * bbin_ * 2);
     }
-    if (ByNodeOnDevice()) {
+    if (plan_.bynode_on_device) {
       bool filt = false;
       const std::vector<uint8_t> m = col_sampler_.ByNodeSampleModes(&fbyn_cnt_, &filt);
       fbyn_reset_ = filt ? 1 : 0;
       fbyn_mode_.Resize(m.size());
       fbyn_mode_.Upload(m.data(), m.size(), stream_);
     }
-    fvoting_ = FrontierVoting();
     if (fvoting_) {
       // voting's local pass: min_data / min_hessian divided by the ranks (reference :61-63, integer division)
       SplitParams sl = MakeArgs().sp;
@@ -2082,7 +1966,7 @@ class DeviceTreeLearner : public TreeLearner {
       // off below 128 leaves; 1: probing from the first tree.
       const char* te = std::getenv("LGAP_SPEC_TUNE");
       const bool tune_small = te == nullptr || te[0] != '0';
-      stune_.on = !distributed_ && (L_ >= 128 || tune_small) && !RawCands() && fnum_forced_ == 0 &&
+      stune_.on = !plan_.distributed && (L_ >= 128 || tune_small) && !plan_.raw_cands && fnum_forced_ == 0 &&
                   spec.empty();
       if (L_ < 128 && te == nullptr) stune_.rest = 64;
     }
@@ -2142,7 +2026,7 @@ class DeviceTreeLearner : public TreeLearner {
     a.hmeta = fhmeta_.get();
     a.red_grid = (num_tiles_ > 1 ? 4 : 2) * num_cu_;  // (wide data: many reduce items per round)
     a.ghmax = ghmax_.get();
-    a.sum_mult = distributed_ && !ffeature_ ? std::max(1, P_) : 1;  // (max-reduced local sums)
+    a.sum_mult = plan_.distributed && !ffeature_ ? std::max(1, P_) : 1;  // (max-reduced local sums)
     {
       const char* e = std::getenv("LGAP_FIXED_SUMBOUND");
       a.sum_bound = e == nullptr || std::atoi(e) != 0;
@@ -2207,18 +2091,18 @@ class DeviceTreeLearner : public TreeLearner {
     }
     a.e_lo = 0;
     a.e_hi = kFrontierKmax;
-    if (RawCands() && fnuep_.size() > 0) {
+    if (plan_.raw_cands && fnuep_.size() > 0) {
       a.cegb_raw = 1;
       a.cegb_tradeoff = config_->cegb_tradeoff;
       a.nkey = fnkey_.get();
       a.ninfo = fninfo_.get();
       a.nuep = fnuep_.get();
-      if (CegbCoupled()) {
+      if (plan_.cegb_coupled) {
         a.cegb_coupled = cegb_coupled_.get();
         a.cegb_used = cegb_used_.get();
         a.cegb_epoch = cegb_epoch_.get();
       }
-      if (CegbLazy()) {
+      if (plan_.cegb_lazy) {
         a.cegb_lazy = cegb_lazy_.get();
         a.lazy_bits = lazy_bits_.get();
         a.lazy_words = lazy_words_;
@@ -2230,17 +2114,17 @@ class DeviceTreeLearner : public TreeLearner {
     a.spec_cap = fspec_cap_;
     a.policy = fpolicy_;
     a.stamps = fstamps_.size() ? fstamps_.get() : nullptr;
-    a.distributed = distributed_ ? 1 : 0;
+    a.distributed = plan_.distributed ? 1 : 0;
     a.kcap = fcaps_on_ ? fkcap_.get() : nullptr;
-    a.kused = distributed_ ? fkused_.get() : nullptr;
-    if (distributed_) {
+    a.kused = plan_.distributed ? fkused_.get() : nullptr;
+    if (plan_.distributed) {
       // the all-reduced level sums of every rank: packed only when the GLOBAL rows fit
       const double gl = a.qbins / 2, hl = a.qconst ? 1 : a.qbins;
       a.qpack = fglobal_rows_ * gl < 2147483647.0 && fglobal_rows_ * hl < 4294967295.0 ? 1 : 0;
     }
     a.sp = MakeArgs().sp;
     a.bynode = use_bynode_ ? bynode_.get() : nullptr;
-    a.byn_draw = frontier_ && ByNodeOnDevice() ? bynode_.get() : nullptr;
+    a.byn_draw = frontier_ && plan_.bynode_on_device ? bynode_.get() : nullptr;
     a.byn_mode = fbyn_mode_.size() ? fbyn_mode_.get() : nullptr;
     a.byn_cnt = fbyn_cnt_;
     a.byn_reset = fbyn_reset_;
@@ -2301,7 +2185,7 @@ class DeviceTreeLearner : public TreeLearner {
   // Data-parallel frontier: sum the round's accumulators of the first `kb` expansions over
   // the ranks (the rest are zero on every rank).
   void FrontierExchange(int kb) {
-    if (!distributed_ || fvoting_ || fowner_) return;
+    if (!plan_.distributed || fvoting_ || fowner_) return;
     AllreduceSumU64(reinterpret_cast<unsigned long long*>(facc_.get()),
                     static_cast<size_t>(std::max(1, std::min(kb, fkmax_))) * AccWordsPerBin() * TB_, stream_);
   }
@@ -2321,7 +2205,7 @@ class DeviceTreeLearner : public TreeLearner {
   // 10M: 289.2 vs 361.0; profiles/r03/dp_pipeline_ab.txt), so the serial order is the default
   // until a multi-GPU node shows the overlap paying for them.
   bool FrontierPipelined(int kb) const {
-    if (!distributed_ || HostStagedDP() || !CommExists() || kb < 2) return false;
+    if (!plan_.distributed || HostStagedDP() || !CommExists() || kb < 2) return false;
     const char* e = std::getenv("LGAP_DP_PIPELINE");
     return e != nullptr && e[0] == '1';
   }
@@ -2355,7 +2239,7 @@ class DeviceTreeLearner : public TreeLearner {
     return static_cast<size_t>(max_bin_) * 2 * sizeof(double) + static_cast<size_t>(cat_p2_) * (2 * sizeof(int) + sizeof(double));
   }
 
-  // Owner-computes data-parallel round (FrontierOwner): histograms + reduce into the per-rank
+  // Owner-computes data-parallel round (fowner_): histograms + reduce into the per-rank
   // chunks, the reduce-scatter, owner-only scans, the per-child bests exchanged. `kb` = the
   // round's expansion bound (the chunk stride the reduce and the reduce-scatter agree on).
   void FrontierOwnerRound(const FArgs& fa, int kb) {
@@ -2378,8 +2262,8 @@ class DeviceTreeLearner : public TreeLearner {
 
   // Feature parallel: this rank's per-child bests all-gathered (the select takes the best over
   // ranks in its phase A: no merge launch). CEGB's raw per-feature candidates would need every
-  // feature's scan on every rank: those configurations never reach these modes (FrontierOwner,
-  // the factory's FrontierServes).
+  // feature's scan on every rank: those configurations never reach these modes (the
+  // engine plan keeps them on the all-reduce or the host policy).
   void FrontierFeatureExchange(const FArgs& fa) {
     if (fa.cegb_raw) Log::Fatal("frontier feature exchange: raw CEGB candidates are not exchanged");
     if (fa.xg) return;  // (xGMI: the select pushes the per-child bests and merges the ranks' records)
@@ -2447,10 +2331,10 @@ class DeviceTreeLearner : public TreeLearner {
       HIP_CHECK(hipGetLastError());
       // the tree setup and k_root_final's fold of the partials in one launch
       LaunchFrontierInitRoot(fa, ra.root_part, root_blocks, ghmax_.get(), stream_);
-      if (distributed_ && fa.xg) {
+      if (plan_.distributed && fa.xg) {
         // global root sums and gradient maxima, exchanged in-kernel (xGMI transport)
         LaunchFrontierXRoot(fa, ghmax_.get(), stream_);
-      } else if (distributed_) {
+      } else if (plan_.distributed) {
         // global root sums and gradient maxima (the fixed-point scales must agree on all ranks)
         AllreduceSumF64(reinterpret_cast<double*>(flsum_), 2, stream_);
         AllreduceMaxU32(ghmax_.get(), 4, stream_);
@@ -2471,7 +2355,7 @@ class DeviceTreeLearner : public TreeLearner {
       // round r + 1 of the tree (main replay) has at most 2^r open nodes, and at most its cap
       int kb = prologue && r < 7 ? (1 << r) : fkmax_;
       if (prologue && fcaps_on_ && r + 1 < kFrontierRoundCap) kb = std::min(kb, fcap_host_[r + 1]);
-      fstat_ar_exps_ += distributed_ ? std::max(1, std::min(kb, fkmax_)) : 0;
+      fstat_ar_exps_ += plan_.distributed ? std::max(1, std::min(kb, fkmax_)) : 0;
       EnqueueFrontierRound(fa, kb);
     }
   }
@@ -2505,7 +2389,7 @@ class DeviceTreeLearner : public TreeLearner {
   // each until it is. Results: the committed splits, the final leaf ranges, the root output.
   // a stream carrying RCCL collectives: a lost peer must not hang the process
   void FrontierSync() {
-    if ((distributed_ || ffeature_) && !HostStagedDP() && !FrontierXg()) {
+    if ((plan_.distributed || ffeature_) && !HostStagedDP() && !FrontierXg()) {
       WatchedStreamSync(stream_, CommTimeoutSeconds(config_->time_out), "frontier tree growth (RCCL all-reduce)");
     } else {
       HIP_CHECK(hipStreamSynchronize(stream_));
@@ -2517,13 +2401,13 @@ class DeviceTreeLearner : public TreeLearner {
     // sequential chain); the host-staged rehearsal transport synchronises inside its exchange
     // (feature parallel exchanges candidates over collectives too, without distributed rows)
     // (the xGMI transport keeps every exchange inside the kernels: a tree replays as one graph)
-    const bool comm = (distributed_ || ffeature_) && !FrontierXg();
+    const bool comm = (plan_.distributed || ffeature_) && !FrontierXg();
     const bool use_graph = config_->device_use_graph && (!comm || (DPGraphEnabled() && !HostStagedDP()));
     if (use_graph && comm && !fgraphs_.empty() && graph_comm_ != ActiveComm()) InvalidateGraph();
     if (use_graph && comm) graph_comm_ = ActiveComm();
     // per-round caps need the eager enqueue (the all-reduce sizes change from tree to tree)
-    fcaps_on_ = distributed_ && !use_graph && !FrontierXg();
-    if (distributed_) {
+    fcaps_on_ = plan_.distributed && !use_graph && !FrontierXg();
+    if (plan_.distributed) {
       if (fkused_.size() < static_cast<size_t>(kFrontierRoundCap)) {
         fkused_.Resize(kFrontierRoundCap);
         fkcap_.Resize(kFrontierRoundCap);
@@ -2568,7 +2452,7 @@ class DeviceTreeLearner : public TreeLearner {
       // (intermediate monotone: a split may wait on a round of rescans and one of expansion)
       // (a bound against a replay that stops advancing; each split needs at most an expansion, a
       // rescan and a re-expansion round, several per split when its speculation is voided)
-      if (launched > (MonoInter() ? 6 : 1) * L_ + 2 * kCont) Log::Fatal("frontier tree: not finished after %d rounds", launched);
+      if (launched > (plan_.mono_inter ? 6 : 1) * L_ + 2 * kCont) Log::Fatal("frontier tree: not finished after %d rounds", launched);
       if (use_graph) {
         if (!fcont_) fcont_ = CaptureFrontier(kCont, false);
         HIP_CHECK(hipGraphLaunch(fcont_, stream_));
@@ -2610,7 +2494,7 @@ class DeviceTreeLearner : public TreeLearner {
       Log::Fatal("xGMI exchange (%s) timed out on rank %d after %.0f s: a peer stopped training",
                  kinds[std::min<unsigned>(hbar[3] - 1u, kFXKinds - 1)], rank_, XTimeoutSeconds());
     }
-    if (distributed_) {
+    if (plan_.distributed) {
       std::memcpy(fkused_hist_[fkused_trees_ % 4], hh->kused, sizeof(int) * kFrontierRoundCap);
       ++fkused_trees_;
     }
@@ -2688,10 +2572,10 @@ class DeviceTreeLearner : public TreeLearner {
     // enqueue stays ahead of the ~40 us splits. The host-staged rehearsal transport
     // synchronises inside its all-reduce and is never captured.
     // the xGMI transport keeps every exchange inside the kernels: the tree replays as one graph
-    const bool collectives = owner_scan_ || voting_;
+    const bool collectives = plan_.owner_scan || plan_.voting;
     const bool use_graph = config_->device_use_graph && (!collectives || (DPGraphEnabled() && !HostStagedDP()));
     if (use_graph) {
-      if (graph_exec_ && distributed_ && graph_comm_ != ActiveComm()) InvalidateGraph();
+      if (graph_exec_ && plan_.distributed && graph_comm_ != ActiveComm()) InvalidateGraph();
       if (!graph_exec_) CaptureGraph();
       HIP_CHECK(hipGraphLaunch(graph_exec_, stream_));
     } else {
@@ -2721,9 +2605,9 @@ class DeviceTreeLearner : public TreeLearner {
   }
 
   std::string DeviceName() const override {
-    if (!owner_scan_ && !voting_) {
-      if (!FrontierEligible()) return device_name_;
-      if (MonoInter()) return device_name_ + " [frontier engine, intermediate monotone walk + rescans]";
+    if (!plan_.owner_scan && !plan_.voting) {
+      if (!frontier_) return device_name_;
+      if (plan_.mono_inter) return device_name_ + " [frontier engine, intermediate monotone walk + rescans]";
       return device_name_ + (QuantHist() ? " [frontier engine, int8-level histograms]" : " [frontier engine]");
     }
     return device_name_ + " [" + ParallelDesc() + "]";
@@ -2849,7 +2733,7 @@ class DeviceTreeLearner : public TreeLearner {
     HIP_CHECK(hipStreamSynchronize(stream_));
     std::vector<double> flat(2 * nl);
     for (int l = 0; l < nl; ++l) flat[2 * l] = st[l].x, flat[2 * l + 1] = st[l].y;
-    if (distributed_) Network::GlobalSum(&flat);
+    if (plan_.distributed) Network::GlobalSum(&flat);
     SplitParams p = MakeArgs().sp;
     p.path_smooth = 0.0;
     for (int l = 0; l < nl; ++l) {
@@ -3308,7 +3192,7 @@ class DeviceTreeLearner : public TreeLearner {
       else k_hist<2, 0><<<hgrid, kHistThreads, hist_lds_bytes_, stream_>>>(a);
     }
     HIP_CHECK(hipGetLastError());
-    if (owner_scan_ && data_parallel_ && collective) {
+    if (plan_.owner_scan && plan_.mode == ParallelMode::kData && collective) {
       // owner reduce-scatter of the smaller child's histogram (xGMI: inside k_hist_owner)
       const int ogrid = DivUp(static_cast<long long>(P_) * 2 * bbin_, 64);
       if (use_dp_) {
@@ -3330,14 +3214,14 @@ class DeviceTreeLearner : public TreeLearner {
   }
 
   void LaunchScan(const Args& a) {
-    if (voting_) {
+    if (plan_.voting) {
       LaunchVoting(a);
       return;
     }
     LaunchReduceScan(a, Fmax_);
     HIP_CHECK(hipGetLastError());
     // complete the candidate table (xGMI: inside k_reduce_scan)
-    if (owner_scan_ && P_ > 1) AllGatherInPlace(cand_.get(), cand_stride_, stream_);
+    if (plan_.owner_scan && P_ > 1) AllGatherInPlace(cand_.get(), cand_stride_, stream_);
   }
 
   void LaunchReduceScan(const Args& a0, int grid) {
@@ -3464,8 +3348,6 @@ class DeviceTreeLearner : public TreeLearner {
     }
     // features / groups
     std::vector<DevFeature> feats(std::max(F_, 1));
-    max_cat_bin_ = 1;
-    has_cat_ = false;
     for (int f = 0; f < F_; ++f) {
       const FeatureInfo& fi = data_->feature(f);
       DevFeature& d = feats[f];
@@ -3480,14 +3362,12 @@ class DeviceTreeLearner : public TreeLearner {
       d.bin_type = static_cast<int8_t>(fi.bin_type);
       d.monotone = fi.monotone;
       d.penalty = fi.penalty;
-      if (fi.bin_type == BinType::Categorical) {
-        has_cat_ = true;
-        max_cat_bin_ = std::max(max_cat_bin_, fi.num_bin);
-      }
     }
     h_feats_ = feats;
-    max_bin_ = 2;
-    for (int f = 0; f < F_; ++f) max_bin_ = std::max(max_bin_, data_->feature(f).num_bin);
+    // (the widest feature and the widest categorical one: the plan's view of the data, ShapeOf)
+    has_cat_ = plan_in_.shape.has_categorical;
+    max_cat_bin_ = plan_in_.shape.max_cat_bin;
+    max_bin_ = plan_in_.shape.max_bin;
     // k_reduce_scan: two full histograms + 16x64 partials + 2 categorical sort arrays (bin, ctr)
     cat_p2_ = 1;
     if (has_cat_) {
@@ -3530,7 +3410,7 @@ class DeviceTreeLearner : public TreeLearner {
     // 150 KB block per CU (1024 threads in the frontier). A/B, LambdaRank 5M x 300 (255 bins,
     // 11 tiles of 7 dwords at 56 KB): 79.8 -> 92.2 it/s; GOSS 12.5M x 500 (63 bins, 5 tiles
     // of 28 dwords) keeps 56 KB (150 KB measured 76.8 -> 61.8).
-    if (env_kb == 0 && mode_ == DevParallel::kSerial && num_tiles_ > 1 && min_tile_dw_ < 16) {
+    if (env_kb == 0 && plan_.mode == ParallelMode::kSerial && num_tiles_ > 1 && min_tile_dw_ < 16) {
       big_tiles_ = true;
       PlanTiles(150 * 1024);
     }
@@ -3715,7 +3595,7 @@ class DeviceTreeLearner : public TreeLearner {
     // the exchange buffer that the peers push into)
     cand_.Resize(static_cast<size_t>(P_) * cand_stride_);
     cand_.Zero(stream_);
-    if (voting_) {
+    if (plan_.voting) {
       const size_t es = use_dp_ ? 8 : 4;
       vcand_.Resize(static_cast<size_t>(vcand_stride_));
       vcand_.Zero(stream_);
@@ -3750,12 +3630,12 @@ class DeviceTreeLearner : public TreeLearner {
       }
     }
     rx_.Resize(std::max<size_t>(1, 2 * static_cast<size_t>(bbin_) * (use_dp_ ? 8 : 4)));
-    stage_.Resize(owner_scan_ ? static_cast<size_t>(P_) * 2 * bbin_ * (use_dp_ ? 8 : 4) : 1);
+    stage_.Resize(plan_.owner_scan ? static_cast<size_t>(P_) * 2 * bbin_ * (use_dp_ ? 8 : 4) : 1);
     use_ic_ = !config_->interaction_constraints_vector.empty();
     if (use_ic_) {
       const auto& sets = config_->interaction_constraints_vector;
       // the frontier holds up to 256 sets (words of 64); the sequential chain's one word, 64
-      // (TreeLearner::Create routes more than 64 sets to the frontier or the host policy)
+      // (the engine plan routes more than 64 sets to the frontier or the host policy)
       if (sets.size() > 64 * static_cast<size_t>(kFrontierIcWords)) {
         Log::Fatal("The HIP learner holds at most %d interaction constraint sets", 64 * kFrontierIcWords);
       }
@@ -3861,7 +3741,7 @@ class DeviceTreeLearner : public TreeLearner {
     // 0: separate k_post kernel, 1: block 0 after its tiles, 2: first spare block
     a.fuse_post = config_->device_post_mode;
     a.stamps = stamps_.size() ? stamps_.get() : nullptr;
-    a.distributed = distributed_ ? 1 : 0;
+    a.distributed = plan_.distributed ? 1 : 0;
     a.use_monotone = config_->monotone_constraints.empty() ? 0 : 1;
     a.monotone_penalty = config_->monotone_penalty;
     a.cegb_split = CegbPenalty::Enabled(config_) ? config_->cegb_tradeoff * config_->cegb_penalty_split : 0.0;
@@ -3875,12 +3755,12 @@ class DeviceTreeLearner : public TreeLearner {
     a.P = P_;
     a.rank = rank_;
     a.Fmax = Fmax_;
-    a.cand_rows = owner_scan_ ? P_ : 1;
-    a.own_feat = owner_scan_ ? own_feat_.get() : nullptr;
+    a.cand_rows = plan_.owner_scan ? P_ : 1;
+    a.own_feat = plan_.owner_scan ? own_feat_.get() : nullptr;
     a.cand = cand_.get();
     a.cand_stride = cand_stride_;
     a.cand_key_bytes = cand_key_bytes_;
-    if (voting_) {
+    if (plan_.voting) {
       // the partition's select and k_vote_scan use the global (elected) table
       a.cand = vcand_.get();
       a.Fmax = topk_;
@@ -3898,7 +3778,7 @@ class DeviceTreeLearner : public TreeLearner {
     }
     // data parallel: the scan reads the reduce-scattered owner row; single GPU / feature parallel:
     // the local slab rows
-    a.scan_src = (owner_scan_ && data_parallel_) ? 1 : 0;
+    a.scan_src = (plan_.owner_scan && plan_.mode == ParallelMode::kData) ? 1 : 0;
     a.rx = rx_.get();
     a.own_bin0 = h_bin_lo_.empty() ? 0 : h_bin_lo_[rank_];
     a.bbin = bbin_;
@@ -3930,7 +3810,7 @@ class DeviceTreeLearner : public TreeLearner {
     const int root_blocks = RootBlocks();
     k_root_sums<<<root_blocks, kRootThreads, 0, s>>>(a);
     k_root_final<<<1, kRootThreads, 0, s>>>(a, root_blocks);
-    if (distributed_) AllreduceSumF64(reinterpret_cast<double*>(lsum_.get()), 2, s);
+    if (plan_.distributed) AllreduceSumF64(reinterpret_cast<double*>(lsum_.get()), 2, s);
     LaunchHist(a);
     LaunchScan(a);
     for (int it = 0; it < L_ - 1; ++it) {
@@ -3959,7 +3839,7 @@ class DeviceTreeLearner : public TreeLearner {
     HIP_CHECK(hipStreamEndCapture(stream_, &g));
     HIP_CHECK(hipGraphInstantiate(&graph_exec_, g, nullptr, nullptr, 0));
     HIP_CHECK(hipGraphDestroy(g));
-    graph_comm_ = distributed_ ? ActiveComm() : nullptr;  // the captured collectives' communicator
+    graph_comm_ = plan_.distributed ? ActiveComm() : nullptr;  // the captured collectives' communicator
   }
 
   static bool DPGraphEnabled() {
@@ -4116,15 +3996,15 @@ class DeviceTreeLearner : public TreeLearner {
   DevBuf<double> lin_partial_, lin_out_, lin_tcoef_, lin_tcnst_;
   DevBuf<long long> lin_usable_;
   const LinearLeaves* lin_pending_ = nullptr;  // set around TraverseLinear's traversal
-  // feature-parallel frontier (FrontierFeature)
+  // feature-parallel frontier (FrontierMode::kFeature)
   bool ffeature_ = false;
-  bool fowner_ = false;  // data-parallel owner-computes rounds (FrontierOwner)
+  bool fowner_ = false;  // data-parallel owner-computes rounds (FrontierMode::kDataOwner)
   int fown_n_ = 0;
   DevBuf<int> fown_list_, fown_b0_;
   DevBuf<unsigned long long> facc_recv_;
   DevBuf<uint8_t> ffowned_;
   DevBuf<FPairBest> ffpb_;
-  // voting-parallel frontier (FrontierVoting)
+  // voting-parallel frontier (FrontierMode::kVoting)
   bool fvoting_ = false;
   DevBuf<double2> flsum_loc_;
   DevBuf<unsigned long long> fltot_;
@@ -4236,8 +4116,6 @@ class DeviceTreeLearner : public TreeLearner {
   DevBuf<unsigned long long> fstamps_;
   const float2* fgraph_gh_ = nullptr;
   const Config* config_;
-  bool data_parallel_ = false;
-  bool distributed_ = false;
   const Dataset* data_ = nullptr;
   int N_ = 0, F_ = 0, G_ = 0, TB_ = 0, width_ = 1, stride_dw_ = 1, L_ = 2, K_ = 1;
   int row_align_ = 0;     // tile / padded-row alignment in dwords (RowAlign), 0: none
@@ -4303,15 +4181,17 @@ class DeviceTreeLearner : public TreeLearner {
   DevBuf<unsigned> bar_;
   DevBuf<SplitKey> leaf_key_;
   // owner-computes parallel modes
-  DevParallel mode_ = DevParallel::kSerial;
-  bool owner_scan_ = false;
+  // tree_learner as configured; the engine plan of the current configuration and its inputs (Replan)
+  const std::string learner_type_;
+  const bool routed_;
+  PlanInputs plan_in_;
+  EnginePlan plan_;
   int P_ = 1, rank_ = 0, Fmax_ = 1, bbin_ = 1, cand_stride_ = 0, cand_key_bytes_ = 0;
   std::vector<int> h_bin_lo_, h_own_feat_;
   DevBuf<int> own_feat_, bin_lo_;
   DevBuf<char> cand_, rx_, stage_;
   DevBuf<unsigned> xcnt_;
   // voting parallel
-  bool voting_ = false;
   int topk_ = 1, vcap_ = 2, vcand_key_bytes_ = 0, vcand_stride_ = 0;
   size_t vote_local_lds_ = 0, vote_pack_lds_ = 0, vote_scan_lds_ = 0;
   DevBuf<char> vcand_, vhist_;
@@ -4435,54 +4315,23 @@ class DeviceTreeLearner : public TreeLearner {
 }  // namespace
 
 std::unique_ptr<TreeLearner> CreateDeviceTreeLearner(const Config* config, const std::string& parallel_mode) {
-  if (parallel_mode == "serial") return std::make_unique<DeviceTreeLearner>(config, DevParallel::kSerial);
-  if (parallel_mode == "data") return std::make_unique<DeviceTreeLearner>(config, DevParallel::kData);
-  if (parallel_mode == "feature") return std::make_unique<DeviceTreeLearner>(config, DevParallel::kFeature);
-  if (parallel_mode == "voting") return std::make_unique<DeviceTreeLearner>(config, DevParallel::kVoting);
-  Log::Fatal("Unknown tree learner type %s", parallel_mode.c_str());
-  return nullptr;
+  return std::make_unique<DeviceTreeLearner>(config, parallel_mode, /*routed=*/true);
 }
 
-bool LinearOnDevice(const Config* config, const Dataset* train, const std::string& learner_type) {
-  if (learner_type != "serial" || config->use_quantized_grad || train == nullptr || !train->has_raw()) return false;
-  // the Gram tile holds <= kLinMaxM - 1 branch features: bounded by the features, the leaves
-  // and the depth
-  long long k = std::min<long long>(train->num_features(), std::max(1, config->num_leaves) - 1);
-  if (config->max_depth > 0) k = std::min<long long>(k, config->max_depth);
-  return k + 1 <= kLinMaxM;
-}
-
-namespace {
-bool FrontierShapeFor(const Config* config, const Dataset* train, bool raw, bool mono_inter = false) {
-  if (config->interaction_constraints_vector.size() > 64 * static_cast<size_t>(kFrontierIcWords)) return false;
-  if (train == nullptr) return config->num_leaves <= 256;  // (no data yet: a conservative shape)
-  int max_bin = 2, max_cat_bin = 1;
-  for (int f = 0; f < train->num_features(); ++f) {
-    const FeatureInfo& fi = train->feature(f);
-    max_bin = std::max(max_bin, fi.num_bin);
-    if (fi.bin_type == BinType::Categorical) max_cat_bin = std::max(max_cat_bin, fi.num_bin);
-  }
-  return FrontierShapeFits(std::max(2, config->num_leaves), train->num_total_bin(), train->num_features(), max_bin,
-                           max_cat_bin, raw, mono_inter);
-}
-}  // namespace
-
-bool FrontierServes(const Config* config, const Dataset* train, const std::string& learner_type) {
-  if (learner_type != "serial" || config->feature_fraction_bynode < 1.0 || config->extra_trees) return false;
-  const bool cegb_raw = !config->cegb_penalty_feature_coupled.empty() || !config->cegb_penalty_feature_lazy.empty();
-  return FrontierShapeFor(config, train, cegb_raw);
-}
-
-bool FrontierServesMonoInter(const Config* config, const Dataset* train, const std::string& learner_type) {
-  if (learner_type != "serial" || config->feature_fraction_bynode < 1.0 || config->extra_trees) return false;
-  if (!config->forcedsplits_filename.empty() || CegbPenalty::Enabled(config)) return false;
-  if (config->monotone_constraints_method != "intermediate") return false;
-  return FrontierShapeFor(config, train, false, true);
-}
-
-bool FrontierServesByNode(const Config* config, const Dataset* train, const std::string& learner_type) {
-  if (learner_type != "serial" || config->extra_trees) return false;
-  return FrontierShapeFor(config, train, true);  // (by-node sampling keeps raw candidates)
+PlanInputs GatherPlanInputs(const std::string& learner_type, bool linear_tree, const Config* config,
+                            const Dataset* train) {
+  PlanInputs in;
+  in.learner_type = learner_type;
+  in.linear_tree = linear_tree;
+  in.config = config;
+  in.shape = ShapeOf(train);
+  in.device_total_memory = DeviceTotalMemory();
+  in.env = ReadRoutingEnv();
+  in.comm_exists = CommExists();
+  in.comm_active = CommActive();
+  in.host_staged = HostStagedDP();
+  in.dp_ranks = DpSize();
+  return in;
 }
 
 namespace {
@@ -4495,7 +4344,7 @@ class DeviceHistogramBackend final : public HistogramBackend {
     cfg_.gpu_use_dp = user->gpu_use_dp;
     cfg_.gpu_device_id = user->gpu_device_id;
     cfg_.device_hist_blocks = user->device_hist_blocks;
-    learner_ = std::make_unique<DeviceTreeLearner>(&cfg_, DevParallel::kSerial);
+    learner_ = std::make_unique<DeviceTreeLearner>(&cfg_, "serial");
     learner_->Init(data, false);
     data_ = data;
   }
@@ -4621,7 +4470,7 @@ std::unique_ptr<HistogramBackend> CreateHistogramBackend(const Config* config, c
 void TestFrontierHist(const Dataset* data, const Config& config, const float* grad, const float* hess, const int* rows,
                       const int* offsets, int k, double* out, uint16_t* levels) {
   if (DeviceCount() <= 0) Log::Fatal("TestFrontierHist: no AMD GPU visible to HIP");
-  DeviceTreeLearner learner(&config, DevParallel::kSerial);
+  DeviceTreeLearner learner(&config, "serial");
   learner.Init(data, false);
   learner.TestFrontierHist(grad, hess, rows, offsets, k, out, levels);
 }
@@ -4629,7 +4478,7 @@ void TestFrontierHist(const Dataset* data, const Config& config, const float* gr
 void TestFrontierScan(const Dataset* data, const Config& config, const float* grad, const float* hess, double* out,
                       double* ref) {
   if (DeviceCount() <= 0) Log::Fatal("TestFrontierScan: no AMD GPU visible to HIP");
-  DeviceTreeLearner learner(&config, DevParallel::kSerial);
+  DeviceTreeLearner learner(&config, "serial");
   learner.Init(data, false);
   learner.TestFrontierScan(grad, hess, out, ref);
 }
@@ -4638,7 +4487,7 @@ void TestFrontierPartition(const Dataset* data, const Config& config, const int*
                            const int* feats, const int* thr, const int* dleft, const uint32_t* catbits, int* out_rows,
                            int* out_left, int* exp_rows, int* exp_left) {
   if (DeviceCount() <= 0) Log::Fatal("TestFrontierPartition: no AMD GPU visible to HIP");
-  DeviceTreeLearner learner(&config, DevParallel::kSerial);
+  DeviceTreeLearner learner(&config, "serial");
   learner.Init(data, false);
   learner.TestFrontierPartition(rows, offsets, k, feats, thr, dleft, catbits, out_rows, out_left, exp_rows, exp_left);
 }
@@ -4649,7 +4498,7 @@ void DeviceHistogram(const Dataset* data, const float* grad, const float* hess, 
   Config cfg;
   cfg.num_leaves = 2;
   cfg.verbosity = -1;
-  DeviceTreeLearner learner(&cfg, DevParallel::kSerial);
+  DeviceTreeLearner learner(&cfg, "serial");
   learner.Init(data, false);
   learner.TestHistogram(grad, hess, rows, num_rows, out);
 }

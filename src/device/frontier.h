@@ -53,21 +53,20 @@
 
 #include <cstdint>
 
+#include "device/frontier_shape.h"
 #include "device/tree_kernels.h"
 #include "lgap/split_math.h"
 
 namespace lgap {
 namespace device {
 
-constexpr int kFrontierKmax = 64;   // expansions per round (compile-time cap)
 #ifndef LGAP_FRONTIER_BUFS
 #define LGAP_FRONTIER_BUFS 4
 #endif
 constexpr int kFrontierBufs = LGAP_FRONTIER_BUFS;  // depth-indexed row-index buffers
 constexpr int kFrontierIdx = kFrontierBufs + 1;    // index buffers by id: depth buffers {0, 1, 3, ...}, bag 2
 constexpr int kFrontierRoundCap = 64;  // rounds with their own expansion cap (later rounds: kmax)
-constexpr int kFrontierMaxNodes = 4096;  // computed-node capacity of the select's LDS image
-constexpr int kFrontierIcWords = 4;      // interaction-constraint sets on the frontier: 4 x 64
+// (kFrontierKmax, kFrontierMaxNodes, kFrontierIcWords and the select's LDS sizes: frontier_shape.h)
 
 // Fixed-point exponent e of a sum over `rows` rows of values with max |v| = vmax and
 // sum |v| <= vsum over ALL rows: the largest e with 2^e * min(rows * vmax, vsum) <= limit,
@@ -82,13 +81,6 @@ __host__ __device__ inline int FixedPointExp(double limit, double rows, float vm
   int e;
   (void)frexp(limit / b, &e);
   return e - 1;
-}
-
-// entries of the select's sort of the alive nodes: a power of two >= C (C <= kFrontierMaxNodes)
-__host__ __device__ inline int FrontierSortCap(int C) {
-  int p = 64;
-  while (p < C) p <<= 1;
-  return p;
 }
 
 // index-buffer id of depth buffer j (0..3)
@@ -394,13 +386,6 @@ __host__ __device__ inline size_t FrontierScanWaveBytes(int max_bin, int cat_p2)
   return (b + 15) & ~static_cast<size_t>(15);
 }
 void LaunchFrontierSelect(const FArgs& a, hipStream_t s);
-// extra LDS of the intermediate-monotone select (after FrontierSelectLds): per-leaf current and
-// scan bounds, per-node thresholds, the committed node's ancestor levels, per-feature monotone
-// types
-__host__ __device__ inline size_t FrontierSelectMonoLds(int C, int L, int F) {
-  return 16 + static_cast<size_t>(L) * (2 * 16 + 3 * sizeof(int) + 1) + static_cast<size_t>(C) * sizeof(int) +
-         static_cast<size_t>(F) + 16;
-}
 // CEGB lazy penalties: unmarked-row counts of the round's smaller children; after a tree, the
 // final leaves' rows marked for the features on their paths
 void LaunchFrontierLazyCounts(const FArgs& a, hipStream_t s);
@@ -423,13 +408,6 @@ void LaunchFrontierXRoot(const FArgs& a, unsigned* ghmax, hipStream_t s);
 void LaunchFrontierXSelfTest(const FArgs& a, int round, int nvals, unsigned* err, hipStream_t s);
 // one-time kernel attributes (dynamic LDS above 64 KiB)
 void FrontierSetLds(size_t hist_lds, size_t scan_lds, bool use_dp, int width);
-// dynamic LDS of k_f_select (CEGB coupled penalties add F bytes of used flags after it)
-__host__ __device__ inline size_t FrontierSelectLds(int C, int L) {
-  return static_cast<size_t>(C) * (sizeof(double) + 6 * sizeof(int) + 1) + 64 +
-         static_cast<size_t>(L) * (3 * sizeof(int) + sizeof(double) + sizeof(int)) + 64 +
-         static_cast<size_t>(FrontierSortCap(C)) * (sizeof(double) + sizeof(int));
-}
-
 
 }  // namespace device
 }  // namespace lgap

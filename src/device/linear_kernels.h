@@ -11,12 +11,13 @@
 
 #include <cstdint>
 
+#include "device/frontier_shape.h"
 #include "device/leaf_kernels.h"
 
 namespace lgap {
 namespace device {
 
-constexpr int kLinMaxM = 63;  // unknowns per leaf: <= 62 branch features + the constant
+// (kLinMaxM, the unknowns per leaf: frontier_shape.h)
 constexpr int kLinDim = 64;   // [A | c] in up to four 16-wide tiles per dimension (c = column m)
 
 struct LinearGramArgs {

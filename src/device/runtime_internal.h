@@ -17,6 +17,9 @@ bool CommExists();
 // LGAP_DEVICE_DP_TRANSPORT=host with a multi-rank host Network and no RCCL
 // communicator: the device data-parallel learner stages its collectives through
 // host memory (lets several ranks share one GPU to rehearse the multi-rank path).
+// Reads the variable once, at first use, unlike the routing knobs (engine_plan.h
+// ReadRoutingEnv, re-read per training): it gates the transport of every collective of the
+// process, not which engine trains.
 bool HostStagedDP();
 // In-place sum all-reduce of device doubles on `stream` (no-op without a communicator).
 void AllreduceSumF64(double* dev_ptr, size_t count, hipStream_t stream);

@@ -128,7 +128,7 @@ struct Args {
   char* cand;           // candidate table [P] blocks of cand_stride bytes (tree_kernels.h)
   int cand_stride;
   int cand_key_bytes;   // SplitKey part of a block (SplitInfo part follows)
-  int scan_src;         // 0: fold the k_hist slab rows; 1: sum the `nparts` owner rows of `rx`
+  int scan_src;         // 0: fold the k_hist slab rows; 1: read the reduce-scattered owner row `rx`
   // split slab fold (scan_src 0): fold_chunks blocks per feature each fold a run of the slab
   // rows into fold_part; the last to arrive on fold_cnt[j] sums the runs and scans
   int fold_chunks, fold_feats;

@@ -10,6 +10,7 @@
 
 #include <cstdint>
 
+#include "device/frontier_shape.h"
 #include "lgap/split_math.h"
 
 namespace lgap {
@@ -87,7 +88,6 @@ struct SplitKey {
 // owns and publishes its candidates as one block; the blocks of all ranks form the
 // candidate table [P][ SplitKey[2][Fmax] | SplitInfo[2][Fmax] ] that every rank's
 // best-leaf select reads (single GPU: P = 1, Fmax = F).
-constexpr int kMaxXRanks = 16;  // xGMI transport: ranks of one node
 
 // xGMI transport: each rank's exchange buffer (IPC-mapped, uncached device memory)
 // holds [histogram receive rows][candidate table][flags][root rows] at identical

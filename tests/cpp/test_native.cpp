@@ -14,8 +14,10 @@
 #include <string>
 #include <vector>
 
+#include "device/engine_plan.h"
 #include "lgap/c_api.h"
 #include "lgap/common.h"
+#include "lgap/log.h"
 #include "lgap/pointwise_metric.h"
 #include "lgap/random.h"
 #include "lgap/split_math.h"
@@ -238,8 +240,268 @@ void TestBinPiecesMatchDenseBounds() {
   }
 }
 
+// Engine routing table (device/engine_plan.h). Every row's expectation was recorded from the
+// commit before the planner, whose three copies of the decision it replaced: the factory-level
+// columns (host reason, device scans, pool budget) from that commit's HostPolicyReason /
+// DeviceScansServe / FrontierServes* run on the same inputs, the learner-level columns (engine,
+// exchange, xGMI) by reading DeviceTreeLearner there; `src` cites those lines of that commit's
+// device_learner.hip. Base shape: 28 numerical features of 255 bins, 63 leaves, a 288 GB device.
+struct PlanWant {
+  lgap::device::Engine engine;
+  lgap::device::FrontierMode frontier;  // compared on the device engines
+  const char* reason = nullptr;
+  bool scans = false;
+  double budget = -1.0;
+  bool try_xgmi = false, xgmi_required = false, xgmi_needed = false;
+  bool raw = false, mono = false, byn_dev = false;
+  lgap::device::ParallelMode mode = lgap::device::ParallelMode::kSerial;
+};
+
+struct PlanCase {
+  lgap::Config config;
+  lgap::device::PlanInputs in;
+  PlanCase(const char* learner, const std::string& params) {
+    const bool leaves = params.find("num_leaves") != std::string::npos;
+    config.Set(lgap::Config::Str2Map(((leaves ? "verbosity=-1 " : "verbosity=-1 num_leaves=63 ") + params).c_str()));
+    in.learner_type = learner;
+    in.linear_tree = config.linear_tree;
+    in.shape.has_data = true;
+    Features(28);
+    in.device_total_memory = 288ull << 30;
+  }
+  PlanCase& Features(int f) {
+    in.shape.features = f;
+    in.shape.total_bins = f * 255;
+    in.shape.max_bin = 255;
+    return *this;
+  }
+  // a communicator of `ranks` ranks
+  PlanCase& Comm(int ranks) {
+    in.comm_exists = true;
+    in.comm_active = ranks > 1;
+    in.dp_ranks = ranks;
+    return *this;
+  }
+  PlanCase& Transport(lgap::device::DpTransport t) {
+    in.env.dp_transport = t;
+    return *this;
+  }
+};
+
+template <typename Check>
+void PlanCases(Check check) {
+  using namespace lgap::device;  // NOLINT
+  const Engine kHost = Engine::kHostPolicy, kFront = Engine::kFrontier, kSeq = Engine::kSequential;
+  const FrontierMode kNone = FrontierMode::kNone;
+  const char* kWhyForced = "forced splits";
+  const char* kWhyCegb = "cost-effective gradient boosting (feature penalties)";
+  const char* kWhyMono = "intermediate/advanced monotone constraints (device scans, host constraint walk)";
+  const char* kWhyIc = "interaction constraints with by-node sampling / more than 64 sets off the frontier";
+  const char* kWhyVoteColl = "voting-parallel with extra_trees over collectives";
+  std::string sets65, sets257, pens28;
+  for (int i = 0; i < 257; ++i) {
+    const std::string s = std::string(i ? "," : "") + "[" + std::to_string(i % 28) + "," + std::to_string((i + 1) % 28) + "]";
+    if (i < 65) sets65 += s;
+    sets257 += s;
+  }
+  for (int i = 0; i < 28; ++i) pens28 += std::string(i ? "," : "") + "0.5";
+  const std::string forced = "forcedsplits_filename=forced.json", coupled = "cegb_penalty_feature_coupled=" + pens28;
+  const std::string inter = "monotone_constraints=1,-1,0 monotone_constraints_method=intermediate";
+  const std::string advanced = "monotone_constraints=1,-1,0 monotone_constraints_method=advanced";
+  auto want = [](Engine e, FrontierMode f) {
+    PlanWant w;
+    w.engine = e;
+    w.frontier = f;
+    return w;
+  };
+  auto host = [&](const char* why) {
+    PlanWant w = want(kHost, kNone);
+    w.reason = why;
+    return w;
+  };
+
+  // ---- serial (src :1730-1742 FrontierEligible, :1759 FrontierSerial)
+  check(1, PlanCase("serial", ""), want(kFront, FrontierMode::kSerial));
+  {
+    PlanCase c("serial", "");
+    c.in.env.frontier_off = true;  // src :207
+    check(2, c, want(kSeq, kNone));
+  }
+  // node capacity 4 L + 128 = 4128 > 4096 (src :186-190, :210)
+  check(3, PlanCase("serial", "num_leaves=1000"), want(kSeq, kNone));
+  check(4, PlanCase("serial", "extra_trees=true"), want(kFront, FrontierMode::kSerial));  // src :1734
+  {
+    PlanWant w = want(kFront, FrontierMode::kSerial);
+    w.raw = true;  // src :1745
+    check(5, PlanCase("serial", "feature_fraction_bynode=0.5"), w);
+  }
+
+  // ---- linear leaves (parent LinearOnDevice, src :4446-4453)
+  {
+    PlanCase c("serial", "linear_tree=true num_leaves=31");
+    c.in.shape.has_raw = true;
+    check(6, c, want(kFront, FrontierMode::kSerial));
+    c.in.shape.has_raw = false;
+    check(7, c, host("linear_tree"));
+  }
+  {
+    PlanCase c("serial", "linear_tree=true num_leaves=127");
+    c.Features(100).in.shape.has_raw = true;
+    check(8, c, host("linear_tree"));  // min(100, 126) + 1 > 63
+    PlanCase d("serial", "linear_tree=true num_leaves=127 max_depth=6");
+    d.Features(100).in.shape.has_raw = true;
+    check(9, d, want(kFront, FrontierMode::kSerial));
+  }
+
+  // ---- forced splits (parent FrontierServes, src :4470-4474)
+  check(10, PlanCase("serial", forced), want(kFront, FrontierMode::kSerial));
+  check(11, PlanCase("serial", forced + " feature_fraction_bynode=0.5"), host(kWhyForced));
+  {
+    PlanCase c("serial", forced);
+    c.in.env.frontier_off = true;
+    check(12, c, host(kWhyForced));
+  }
+  check(13, PlanCase("data", forced).Comm(8), host(kWhyForced));
+
+  // ---- CEGB feature penalties
+  {
+    PlanWant w = want(kFront, FrontierMode::kSerial);
+    w.raw = true;  // src :1745, :1758
+    check(14, PlanCase("serial", coupled), w);
+  }
+  check(15, PlanCase("serial", coupled + " interaction_constraints=[0,1],[2,3]"), host(kWhyCegb));
+  check(16, PlanCase("serial", coupled).Features(8193), host(kWhyCegb));
+  check(17, PlanCase("data", coupled).Comm(8), host(kWhyCegb));
+
+  // ---- monotone constraints (parent FrontierServesMonoInter, src :4476-4481; DeviceScansServe)
+  {
+    PlanWant w = want(kFront, FrontierMode::kSerial);
+    w.mono = true;  // src :1748
+    check(18, PlanCase("serial", inter), w);
+  }
+  check(19, PlanCase("serial", inter + " extra_trees=true"), host(kWhyMono));
+  {
+    PlanWant w = host(kWhyMono);
+    w.scans = true;
+    check(20, PlanCase("serial", advanced), w);
+  }
+  check(21, PlanCase("serial", advanced + " " + forced), host(kWhyMono));
+
+  // ---- interaction constraints (parent FrontierServesByNode, src :4483-4486)
+  check(22, PlanCase("serial", "interaction_constraints=" + sets65), want(kFront, FrontierMode::kSerial));
+  check(23, PlanCase("serial", "interaction_constraints=" + sets257), host(kWhyIc));
+  {
+    PlanWant w = want(kFront, FrontierMode::kSerial);
+    w.raw = w.byn_dev = true;  // src :1752
+    check(24, PlanCase("serial", "interaction_constraints=[0,1],[2,3] feature_fraction_bynode=0.5"), w);
+  }
+  check(25, PlanCase("data", "interaction_constraints=[0,1],[2,3] feature_fraction_bynode=0.5").Comm(8), host(kWhyIc));
+
+  // ---- data parallel over a communicator (src :1774-1795 FrontierDP / FrontierOwner, :371-396 SetupTransport)
+  {
+    PlanWant w = want(kFront, FrontierMode::kDataOwner);
+    w.mode = ParallelMode::kData;
+    w.try_xgmi = true;
+    check(26, PlanCase("data", "").Comm(8), w);
+    w.try_xgmi = false;
+    check(28, PlanCase("data", "").Comm(8).Transport(DpTransport::kCollective), w);
+    check(32, PlanCase("data", "").Comm(17), w);  // src :383, more than kMaxXRanks
+    w.frontier = FrontierMode::kDataAllReduce;    // src :1794
+    check(27, PlanCase("data", "").Comm(8).Transport(DpTransport::kAllreduce), w);
+    w = want(kSeq, kNone);
+    w.mode = ParallelMode::kData;
+    PlanCase c("data", "");
+    c.Comm(8).in.env.frontier_dp_off = true;  // src :1776
+    check(29, c, w);
+    check(30, PlanCase("data", "extra_trees=true").Comm(8), w);  // src :1734
+    w.raw = true;
+    check(31, PlanCase("data", "feature_fraction_bynode=0.5").Comm(8), w);  // src :1737
+  }
+
+  // ---- voting parallel over a communicator (src :1801-1803 FrontierVoting)
+  {
+    PlanWant w = want(kFront, FrontierMode::kVoting);
+    w.mode = ParallelMode::kVoting;
+    w.try_xgmi = true;
+    check(33, PlanCase("voting", "").Comm(8), w);
+    check(34, PlanCase("voting", "extra_trees=true").Comm(8).Transport(DpTransport::kCollective), host(kWhyVoteColl));
+    PlanCase c("voting", "extra_trees=true");
+    c.Comm(8).in.env.device_dp_host = true;
+    check(35, c, host(kWhyVoteColl));
+    // KNOWN: the engine needs xGMI, a failed set-up at run time is
+    // fatal (src :389-391) where the host policy could have served it
+    w.xgmi_required = w.xgmi_needed = true;
+    check(36, c.Transport(DpTransport::kXgmi), w);
+    PlanCase d("voting", "extra_trees=true");
+    d.Comm(8).in.shape.has_categorical = true;
+    d.in.shape.max_cat_bin = 16;
+    check(37, d, host("voting-parallel with extra_trees and categorical features"));
+    check(38, PlanCase("voting", "extra_trees=true cegb_penalty_split=0.1").Comm(8),
+          host("voting-parallel with extra_trees and CEGB"));
+    // KNOWN: the frontier cannot hold 1,000 leaves, so voting with a CEGB
+    // split penalty grows on the sequential chain, whose vote scan never subtracts the penalty
+    w = want(kSeq, kNone);
+    w.mode = ParallelMode::kVoting;
+    check(39, PlanCase("voting", "cegb_penalty_split=0.1 num_leaves=1000").Comm(8), w);
+    // KNOWN (the same finding): numerical extra_trees there, whose vote scan never redraws
+    check(42, PlanCase("voting", "extra_trees=true num_leaves=1000").Comm(8), w);
+  }
+
+  // ---- LGAP_FORCE_DEVICE_DP on a one-rank communicator (src :257-268)
+  {
+    PlanCase c("serial", "");
+    c.Comm(1).in.env.force_dp = ForceDP::kData;
+    PlanWant w = want(kFront, FrontierMode::kDataOwner);
+    w.mode = ParallelMode::kData;
+    w.try_xgmi = true;
+    check(40, c, w);
+    c.in.env.force_dp = ForceDP::kVoting;
+    w.frontier = FrontierMode::kVoting;
+    w.mode = ParallelMode::kVoting;
+    check(40, c, w);
+  }
+  // ---- LGAP_DEVICE_HIST_BUDGET_MB=1 at 255 leaves: 16 B x 7,140 bins x 255 leaves = 29 MB
+  {
+    PlanCase c("serial", "num_leaves=255");
+    c.in.env.hist_budget_set = true;
+    c.in.env.hist_budget_mb = 1.0;
+    PlanWant w = host("per-leaf device histograms above the histogram pool");
+    w.budget = 1.0;
+    check(41, c, w);
+  }
+}
+
+// The planner against the table: no Dataset, no device.
+void TestEnginePlan() {
+  using namespace lgap::device;  // NOLINT
+  int rows = 0;
+  const lgap::LogLevel level = lgap::Log::Level();  // (the rows' configurations set verbosity=-1)
+  PlanCases([&](int row, const PlanCase& c, const PlanWant& w) {
+    PlanInputs in = c.in;
+    in.config = &c.config;
+    const EnginePlan p = PlanEngine(in);
+    const int before = g_failures;
+    EXPECT(p.engine == w.engine);
+    EXPECT((p.host_reason == nullptr) == (w.reason == nullptr));
+    if (p.host_reason != nullptr && w.reason != nullptr) EXPECT(std::string(p.host_reason) == w.reason);
+    EXPECT(p.device_scans == w.scans);
+    EXPECT(p.pool_budget_mb == w.budget);
+    if (w.engine != Engine::kHostPolicy) {
+      EXPECT(p.frontier == w.frontier);
+      EXPECT(p.mode == w.mode);
+      EXPECT(p.try_xgmi == w.try_xgmi && p.xgmi_required == w.xgmi_required && p.xgmi_needed == w.xgmi_needed);
+      EXPECT(p.raw_cands == w.raw && p.mono_inter == w.mono && p.bynode_on_device == w.byn_dev);
+    }
+    if (g_failures != before) std::fprintf(stderr, "  ^ engine plan row %d\n", row);
+    ++rows;
+  });
+  EXPECT(rows == 43);
+  lgap::Log::ResetLevel(level);
+}
+
 int main(int argc, char** argv) {
   const std::string data = argc > 1 ? argv[1] : "tests/data";
+  TestEnginePlan();
   TestRandom();
   TestCommon();
   TestPointwiseMetric();
