@@ -34,6 +34,11 @@ $(BUILD)/%.hip.o: src/%.hip $(HEADERS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# predict_device's linear-leaf sums must round like the host's (separate multiply and add). Under
+# -ffp-contract=fast the backend fuses them whatever the source says (the fp contract pragma in
+# predict_pack.h is honoured only from -ffp-contract=on down), so this object is built without it.
+$(BUILD)/device/predict_kernels.hip.o: HIPFLAGS += -ffp-contract=off
+
 $(LIB): $(CPP_OBJS) $(HIP_OBJS)
 	@mkdir -p $(OUT)
 	$(CXX) -o $@ $^ $(LDFLAGS)

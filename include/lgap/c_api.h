@@ -158,6 +158,21 @@ LIGHTGBM_C_EXPORT int LGBM_BoosterPredictForMats(BoosterHandle handle, const voi
                                                  int32_t ncol, int predict_type, int start_iteration,
                                                  int num_iteration, const char* parameter, int64_t* out_len,
                                                  double* out_result);
+// Prediction on the device from a dense row-major matrix (Booster.predict_device). `data` and
+// `out_result` may each be host or device memory (data_on_device / out_on_device). RAW_SCORE and
+// LEAF_INDEX equal LGBM_BoosterPredictForMat bit for bit; NORMAL with host output too (the host's
+// ConvertOutput), NORMAL with device output applies the transform on the device. PREDICT_CONTRIB,
+// pred_early_stop=true and a process without a GPU return -1; nothing falls back to the host.
+LIGHTGBM_C_EXPORT int LGBM_BoosterPredictForMatDevice(BoosterHandle handle, const void* data, int data_type,
+                                                      int32_t nrow, int32_t ncol, int predict_type,
+                                                      int start_iteration, int num_iteration, const char* parameter,
+                                                      int data_on_device, int out_on_device, int64_t* out_len,
+                                                      double* out_result);
+// Test hook: the packed ensemble and row walk of the device path, run in a host loop (no GPU).
+LIGHTGBM_C_EXPORT int LGBM_BoosterTestPackedPredict(BoosterHandle handle, const void* data, int data_type,
+                                                    int32_t nrow, int32_t ncol, int predict_type, int start_iteration,
+                                                    int num_iteration, const char* parameter, int64_t* out_len,
+                                                    double* out_result);
 LIGHTGBM_C_EXPORT int LGBM_BoosterSaveModel(BoosterHandle handle, int start_iteration, int num_iteration,
                                             int feature_importance_type, const char* filename);
 LIGHTGBM_C_EXPORT int LGBM_BoosterSaveModelToString(BoosterHandle handle, int start_iteration, int num_iteration,

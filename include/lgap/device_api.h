@@ -116,5 +116,21 @@ bool DevicePackDense(const Dataset& ds, const void* data, bool f64, int nrow, in
 void* TakeDeviceRows(const Dataset* ds, size_t bytes);
 void ReleaseDeviceRows(const Dataset* ds);
 
+// Prediction from raw feature rows on the device (predict_kernels.hip). `pk` is the packed
+// ensemble of src/device/predict_pack.h; mode is its kPredictRaw / kPredictLeaf. `data` holds
+// nrow x ncol row-major fp32 / fp64 values, `out` nrow x (trees per iteration | trees) doubles;
+// either may be host memory (moved in chunks of at most 256 MiB) or device memory, used in
+// place. With device output a non-null transform is applied to the raw scores on the device
+// (k_predict_convert). The work is complete when the call returns. Fails without a GPU.
+struct PackedEnsemble;
+enum PredictTransformKind : int { kTransformIdentity = 0, kTransformPointwise, kTransformSoftmax, kTransformOVA };
+struct PredictTransform {
+  int kind = kTransformIdentity;
+  int output = 0;        // kTransformPointwise: PwOutput code (lgap/pointwise_metric.h)
+  double sigmoid = 1.0;  // kOutSigmoid / kTransformOVA
+};
+void PredictDense(const PackedEnsemble& pk, const void* data, bool f64, int nrow, int ncol, int mode,
+                  const PredictTransform* transform, bool data_on_device, bool out_on_device, double* out);
+
 }  // namespace device
 }  // namespace lgap

@@ -1296,6 +1296,84 @@ class Booster:
                                               out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
         return self._shape_pred(out, nrow, ptype)
 
+    def predict_device(self, data: Any, start_iteration: int = 0, num_iteration: Optional[int] = None,
+                       raw_score: bool = False, pred_leaf: bool = False, **kwargs: Any) -> Any:
+        """Predict on the GPU from raw feature rows.
+
+        ``data`` is a 2-D numpy array (the result is a numpy array shaped as ``predict``'s) or a
+        2-D torch tensor on the GPU (read in place; the result is a float64 tensor on the same
+        device, shaped ``(nrow,)`` or ``(nrow, k)``). Raw scores and leaf indices equal
+        ``predict`` bit for bit; so does the transformed output for numpy input, while for a
+        device tensor the transform runs on the device. ``pred_contrib`` and ``pred_early_stop``
+        are refused, and so is a process without a GPU: nothing falls back to the host.
+        """
+        if num_iteration is None:
+            num_iteration = self.best_iteration if self.best_iteration > 0 else -1
+        ptype = C_API_PREDICT_NORMAL
+        if raw_score:
+            ptype = C_API_PREDICT_RAW_SCORE
+        if pred_leaf:
+            ptype = C_API_PREDICT_LEAF_INDEX
+        if kwargs.pop("pred_contrib", False):
+            ptype = C_API_PREDICT_CONTRIB  # refused by the library with its own message
+        params = _c_str(param_dict_to_str(kwargs))
+        tensor = None
+        mod = type(data).__module__ or ""
+        if mod == "torch" or mod.startswith("torch."):
+            import torch
+
+            if isinstance(data, torch.Tensor):
+                tensor = data
+        if tensor is not None:
+            import torch
+
+            if not tensor.is_cuda:
+                raise TypeError("predict_device takes a torch tensor on the GPU or a numpy array; "
+                                "pass tensor.numpy() here or to Booster.predict")
+            if tensor.dim() != 2:
+                raise ValueError("Input tensor must be 2 dimensional")
+            if tensor.dtype not in (torch.float32, torch.float64):
+                tensor = tensor.to(torch.float64)
+            tensor = tensor.contiguous()
+            dtype = C_API_DTYPE_FLOAT32 if tensor.dtype == torch.float32 else C_API_DTYPE_FLOAT64
+            nrow, ncol = int(tensor.shape[0]), int(tensor.shape[1])
+            data_ptr = ctypes.c_void_p(tensor.data_ptr())
+        elif isinstance(data, np.ndarray):
+            mat, dtype = _to_float_matrix(data)
+            nrow, ncol = mat.shape
+            data_ptr = mat.ctypes.data_as(ctypes.c_void_p)
+        else:
+            raise TypeError(f"predict_device takes a 2-D numpy array or a torch tensor on the GPU, not "
+                            f"{type(data).__name__}; use Booster.predict for other inputs")
+        n_pred = ctypes.c_int64(0)
+        _check(_LIB.LGBM_BoosterCalcNumPredict(self.handle, ctypes.c_int(nrow), ctypes.c_int(ptype),
+                                               ctypes.c_int(start_iteration), ctypes.c_int(num_iteration),
+                                               ctypes.byref(n_pred)))
+        out_len = ctypes.c_int64(0)
+        if tensor is None:
+            out = np.empty(n_pred.value, dtype=np.float64)
+            _check(_LIB.LGBM_BoosterPredictForMatDevice(
+                self.handle, data_ptr, ctypes.c_int(dtype), ctypes.c_int32(nrow), ctypes.c_int32(ncol),
+                ctypes.c_int(ptype), ctypes.c_int(start_iteration), ctypes.c_int(num_iteration), params,
+                ctypes.c_int(0), ctypes.c_int(0), ctypes.byref(out_len),
+                out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+            return self._shape_pred(out, nrow, ptype)
+        import torch
+
+        with torch.cuda.device(tensor.device):
+            out_t = torch.empty(n_pred.value, dtype=torch.float64, device=tensor.device)
+            # the library works on a stream of its own: the tensor's producer must be done
+            torch.cuda.current_stream().synchronize()
+            _check(_LIB.LGBM_BoosterPredictForMatDevice(
+                self.handle, data_ptr, ctypes.c_int(dtype), ctypes.c_int32(nrow), ctypes.c_int32(ncol),
+                ctypes.c_int(ptype), ctypes.c_int(start_iteration), ctypes.c_int(num_iteration), params,
+                ctypes.c_int(1), ctypes.c_int(1), ctypes.byref(out_len),
+                ctypes.cast(ctypes.c_void_p(out_t.data_ptr()), ctypes.POINTER(ctypes.c_double))))
+        per = n_pred.value // nrow if nrow > 0 else 1
+        if nrow == 0 or (per == 1 and ptype != C_API_PREDICT_LEAF_INDEX):
+            return out_t
+        return out_t.reshape(nrow, per)
+
     def _predict_sparse(self, data, ptype, start_iteration, num_iteration, params) -> np.ndarray:
         csr = data.tocsr()
         nrow = csr.shape[0]

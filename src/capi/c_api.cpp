@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "device/predict_pack.h"
 #include "lgap/arrow.h"
 #include "lgap/boosting.h"
 #include "lgap/common.h"
@@ -269,6 +270,77 @@ void PredictRows(Booster* b, const RowSource& src, int predict_type, int start_i
   }
   errs.Rethrow();
   *out_len = static_cast<int64_t>(n) * per_row;
+}
+
+// ---- prediction over the packed ensemble (device/predict_pack.h): the device kernels, or the
+// same walk in a host loop (on_device = false, the CPU-only test hook)
+void PredictPacked(Booster* b, const void* data, int data_type, int32_t nrow, int32_t ncol, int predict_type,
+                   int start_iteration, int num_iteration, const char* parameter, bool on_device,
+                   bool data_on_device, bool out_on_device, int64_t* out_len, double* out) {
+  std::shared_lock<std::shared_mutex> lk(b->mu_);
+  Config pc = ParseConfig(parameter);
+  GBDT* g = b->boosting_.get();
+  if (predict_type == C_API_PREDICT_CONTRIB) {
+    Log::Fatal("predict_device does not support pred_contrib (SHAP values); use Booster.predict");
+  }
+  if (pc.pred_early_stop) {
+    Log::Fatal("predict_device does not support pred_early_stop; use Booster.predict");
+  }
+  if (predict_type != C_API_PREDICT_NORMAL && predict_type != C_API_PREDICT_RAW_SCORE &&
+      predict_type != C_API_PREDICT_LEAF_INDEX) {
+    Log::Fatal("predict_device: unknown predict_type %d", predict_type);
+  }
+  const bool leaf = predict_type == C_API_PREDICT_LEAF_INDEX;
+  const bool normal = predict_type == C_API_PREDICT_NORMAL;
+  g->InitPredict(start_iteration, num_iteration, false);
+  const int per_row = g->NumPredictOneRow(start_iteration, num_iteration, leaf, false);
+  if (!pc.predict_disable_shape_check && ncol != g->MaxFeatureIdx() + 1 && ncol > 0) {
+    Log::Fatal("The number of features in data (%d) is not the same as it was in training data (%d).\n"
+               "You can set ``predict_disable_shape_check=true`` to discard this error, but please be aware what you are doing.",
+               ncol, g->MaxFeatureIdx() + 1);
+  }
+  if (!leaf && per_row != g->NumModelPerIteration()) {
+    Log::Fatal("predict_device: the objective returns %d values per row from %d trees per iteration; use Booster.predict",
+               per_row, g->NumModelPerIteration());
+  }
+  const device::PackedEnsemble pk = device::PackEnsemble(*g, start_iteration, num_iteration);
+  const int mode = leaf ? device::kPredictLeaf : device::kPredictRaw;
+  const bool f64 = data_type == C_API_DTYPE_FLOAT64;
+  const ObjectiveFunction* obj = g->objective();
+  if (!on_device) {
+    device::PredictPackedHost(pk.View(), data, f64, nrow, ncol, mode, out);
+  } else {
+    // the objective's ConvertOutput as a device transform, used only when the output stays there
+    device::PredictTransform tf;
+    if (normal && obj != nullptr && out_on_device) {
+      int output = 0;
+      double sigmoid = 1.0;
+      if (PointwiseOutputTransform(obj, &output, &sigmoid)) {
+        tf.kind = device::kTransformPointwise;
+        tf.output = output;
+        tf.sigmoid = sigmoid;
+      } else if (obj->device_kind() == DeviceGradKind::kSoftmax) {
+        tf.kind = device::kTransformSoftmax;
+      } else if (obj->device_kind() == DeviceGradKind::kOVA) {
+        tf.kind = device::kTransformOVA;
+        tf.sigmoid = obj->sigmoid();
+      } else if (!obj->IsRanking()) {
+        Log::Fatal("predict_device: objective %s has no device output transform; use raw_score=True or Booster.predict",
+                   obj->GetName());
+      }
+    }
+    device::PredictDense(pk, data, f64, nrow, ncol, mode, &tf, data_on_device, out_on_device, out);
+  }
+  // host output: the host's own ConvertOutput per row, bit-identical to PredictRows
+  if (normal && obj != nullptr && !(on_device && out_on_device)) {
+    std::vector<double> raw(per_row);
+    for (int64_t i = 0; i < nrow; ++i) {
+      double* o = out + i * per_row;
+      std::copy(o, o + per_row, raw.begin());
+      obj->ConvertOutput(raw.data(), o);
+    }
+  }
+  *out_len = static_cast<int64_t>(nrow) * per_row;
 }
 
 }  // namespace
@@ -1029,6 +1101,24 @@ int LGBM_BoosterPredictForMats(BoosterHandle handle, const void** data, int data
   for (int i = 0; i < nrow; ++i) mats.emplace_back(data[i], data_type == C_API_DTYPE_FLOAT64, 1, ncol, true);
   MultiDenseSource src(std::move(mats));
   PredictRows(B(handle), src, predict_type, start_iteration, num_iteration, parameter, out_len, out_result);
+  API_END();
+}
+
+int LGBM_BoosterPredictForMatDevice(BoosterHandle handle, const void* data, int data_type, int32_t nrow, int32_t ncol,
+                                    int predict_type, int start_iteration, int num_iteration, const char* parameter,
+                                    int data_on_device, int out_on_device, int64_t* out_len, double* out_result) {
+  API_BEGIN();
+  PredictPacked(B(handle), data, data_type, nrow, ncol, predict_type, start_iteration, num_iteration, parameter, true,
+                data_on_device != 0, out_on_device != 0, out_len, out_result);
+  API_END();
+}
+
+int LGBM_BoosterTestPackedPredict(BoosterHandle handle, const void* data, int data_type, int32_t nrow, int32_t ncol,
+                                  int predict_type, int start_iteration, int num_iteration, const char* parameter,
+                                  int64_t* out_len, double* out_result) {
+  API_BEGIN();
+  PredictPacked(B(handle), data, data_type, nrow, ncol, predict_type, start_iteration, num_iteration, parameter, false,
+                false, false, out_len, out_result);
   API_END();
 }
 
