@@ -173,6 +173,22 @@ LIGHTGBM_C_EXPORT int LGBM_BoosterTestPackedPredict(BoosterHandle handle, const 
                                                     int32_t nrow, int32_t ncol, int predict_type, int start_iteration,
                                                     int num_iteration, const char* parameter, int64_t* out_len,
                                                     double* out_result);
+// A Dataset from dense matrices that already live on the GPU (torch tensors): nmat row chunks of
+// ncol columns, fp32 or fp64, chunk i holding value (r, c) at data[i][r * row_stride[i] +
+// c * col_stride[i]] (strides in elements, so views are read in place). The bin-construction
+// sample is gathered on the device, the rows are binned there whatever device_type and
+// device_binning say; mappers, bundles and bins equal LGBM_DatasetCreateFromMat(s) on the same
+// values. The caller's work on the chunks must be complete. A process without a GPU returns -1.
+LIGHTGBM_C_EXPORT int LGBM_DatasetCreateFromDeviceMats(int32_t nmat, const void** data, int data_type,
+                                                       const int32_t* nrow, int32_t ncol, const int64_t* row_stride,
+                                                       const int64_t* col_stride, const char* parameters,
+                                                       const DatasetHandle reference, DatasetHandle* out);
+// Test hook: the same construction over host matrices, gather and packing in host loops (no GPU).
+LIGHTGBM_C_EXPORT int LGBM_DatasetTestCreateFromSampledMats(int32_t nmat, const void** data, int data_type,
+                                                            const int32_t* nrow, int32_t ncol,
+                                                            const int64_t* row_stride, const int64_t* col_stride,
+                                                            const char* parameters, const DatasetHandle reference,
+                                                            DatasetHandle* out);
 LIGHTGBM_C_EXPORT int LGBM_BoosterSaveModel(BoosterHandle handle, int start_iteration, int num_iteration,
                                             int feature_importance_type, const char* filename);
 LIGHTGBM_C_EXPORT int LGBM_BoosterSaveModelToString(BoosterHandle handle, int start_iteration, int num_iteration,

@@ -280,6 +280,43 @@ class DenseSource : public RowSource {
   bool row_major_;
 };
 
+// Row chunks of a dense matrix (fp32 / fp64) addressed with element strides, so views are read
+// in place: chunk c holds value (i, j) at data[i * row_stride + j * col_stride]. The chunks
+// live either on the host or on the GPU (torch tensors handed to
+// LGBM_DatasetCreateFromDeviceMats). Device chunks cannot serve GetRow: Dataset::Construct
+// gathers its bin-construction sample with GatherRows and packs the rows on the device.
+struct StridedChunk {
+  const void* data = nullptr;
+  data_size_t nrow = 0;
+  int64_t row_stride = 0;
+  int64_t col_stride = 1;
+};
+
+class StridedChunkSource : public RowSource {
+ public:
+  StridedChunkSource(std::vector<StridedChunk> chunks, bool f64, int ncol, bool on_device);
+  data_size_t num_rows() const override { return total_; }
+  int num_cols() const override { return ncol_; }
+  bool is_f64() const { return f64_; }
+  bool on_device() const { return on_device_; }
+  const std::vector<StridedChunk>& chunks() const { return chunks_; }
+  // host chunks only
+  void GetRow(data_size_t i, std::vector<std::pair<int, double>>* out) const override;
+  // rows `rows[0 .. n)` (global row numbers) as a contiguous row-major [n x ncol] matrix of the
+  // source's dtype in host memory; device chunks are gathered on the GPU and copied once
+  void GatherRows(const int* rows, data_size_t n, void* out) const;
+  // the whole matrix, contiguous row-major, in host memory
+  void CopyToHost(void* out) const;
+
+ private:
+  std::vector<StridedChunk> chunks_;
+  std::vector<data_size_t> starts_;
+  data_size_t total_ = 0;
+  bool f64_;
+  int ncol_;
+  bool on_device_;
+};
+
 // CSR source (indptr int32/int64, indices int32, values f32/f64).
 class CSRSource : public RowSource {
  public:

@@ -12,6 +12,7 @@
 #include "lgap/tree_learner.h"
 
 namespace lgap {
+struct StridedChunk;  // lgap/dataset.h
 namespace device {
 
 // Number of visible MI355X (gfx950) devices; 0 when no GPU / no driver.
@@ -111,6 +112,19 @@ int SampleRowsOnDevice(int mode, int num_rows, int num_class, float* grad, float
 // caller bins on the host).
 bool DevicePackDense(const Dataset& ds, const void* data, bool f64, int nrow, int ncol, uint8_t* host_out,
                      bool keep_device_copy);
+// The same for a matrix that already lives on the GPU (LGBM_DatasetCreateFromDeviceMats): row
+// chunks read in place through element strides, no staging buffers and no upload. A contiguous
+// row-major chunk runs k_pack_tiles / k_pack_rows as above; any other strides run
+// k_pack_strided, which stages the same row tile with lanes along the unit stride. False with
+// a reason in *why_not: the caller copies the matrix to the host. Fails without a GPU or for
+// pointers that are not memory of the current device.
+bool DevicePackResident(const Dataset& ds, const StridedChunk* chunks, int nchunk, bool f64, int ncol,
+                        uint8_t* host_out, bool keep_device_copy, std::string* why_not);
+// k_gather_rows: rows[0 .. n) (global row numbers over the chunks; null: rows first_row ..
+// first_row + n) of device-resident chunks as a contiguous row-major [n x ncol] matrix of the
+// chunks' dtype in host memory.
+void GatherDeviceRows(const StridedChunk* chunks, int nchunk, bool f64, int ncol, const int* rows,
+                      long long first_row, long long n, void* host_out);
 // the device copy of `ds`'s packed rows (ownership moves to the caller; hipFree), or nullptr
 // when none matches `bytes`
 void* TakeDeviceRows(const Dataset* ds, size_t bytes);

@@ -327,6 +327,39 @@ class _ArrowExport:
         _ArrowExport._release(self.schema)
 
 
+def _is_torch_tensor(x: Any) -> bool:
+    """A torch tensor, found by module name so that torch is imported only when one is given."""
+    mod = type(x).__module__ or ""
+    if mod == "torch" or mod.startswith("torch."):
+        import torch
+
+        return isinstance(x, torch.Tensor)
+    return False
+
+
+def _is_device_tensor(x: Any) -> bool:
+    return _is_torch_tensor(x) and x.is_cuda
+
+
+def _device_tensor_list(data: Any) -> Optional[List[Any]]:
+    """``data`` as a list of GPU tensors when it is one GPU tensor or a list of them, else None
+    (a torch tensor on the host keeps taking the ``__array__`` path)."""
+    if _is_device_tensor(data):
+        return [data]
+    if isinstance(data, list) and data and any(_is_device_tensor(t) for t in data):
+        if not all(_is_device_tensor(t) for t in data):
+            raise TypeError("A list of GPU tensors must hold GPU tensors only")
+        return list(data)
+    return None
+
+
+def _metadata_to_host(x: Any) -> Any:
+    """Metadata given as a GPU tensor comes to the host: the objectives initialise from host metadata."""
+    if _is_device_tensor(x):
+        return x.detach().cpu().numpy()
+    return x
+
+
 def _is_pandas(x: Any) -> bool:
     return pd is not None and isinstance(x, pd.DataFrame)
 
@@ -352,6 +385,12 @@ class Dataset:
 
     Reference: python-package/lightgbm/basic.py Dataset (constructor
     arguments, lazy ``construct``, ``create_valid``, field setters).
+
+    Besides the reference's inputs, ``data`` may be a 2-D float32 / float64 torch tensor on the
+    GPU (any strides, read in place) or a list of such tensors stacked by rows: the sample for
+    bin construction is gathered and the rows are binned on the device, with the same mappers,
+    bundles and bins as from the same values as a numpy array. ``label``, ``weight``,
+    ``init_score``, ``group`` and ``position`` may be GPU tensors too; they come to the host.
     """
 
     def __init__(self, data: Any, label: Any = None, reference: Optional["Dataset"] = None, weight: Any = None,
@@ -474,7 +513,10 @@ class Dataset:
         if self.feature_name != "auto" and self.feature_name is not None:
             feature_names = list(self.feature_name)
         out = ctypes.c_void_p()
-        if _is_arrow(data):
+        tensors = _device_tensor_list(data)
+        if tensors is not None:
+            self._lazy_init_device(tensors, feature_names, ref, out)
+        elif _is_arrow(data):
             names = list(data.schema.names) if hasattr(data, "schema") else None
             cat_idx = self._resolve_categorical(feature_names or names, len(names or []))
             with _ArrowExport(data) as ex:
@@ -544,6 +586,45 @@ class Dataset:
                                               ctypes.c_int(1), _c_str(self._build_params(cat_idx)), ref,
                                               ctypes.byref(out)))
 
+    def _lazy_init_device(self, tensors: List[Any], feature_names, ref, out) -> None:
+        """2-D GPU tensors (row chunks, any strides) are sampled and binned where they lie."""
+        import torch
+
+        for t in tensors:
+            if t.dim() != 2:
+                raise ValueError("Input tensor must be 2 dimensional")
+        ncol = int(tensors[0].shape[1])
+        if any(int(t.shape[1]) != ncol for t in tensors):
+            raise ValueError("GPU tensors in a list must have the same number of columns: "
+                             f"{[int(t.shape[1]) for t in tensors]}")
+        if any(t.dtype != tensors[0].dtype for t in tensors):
+            raise ValueError(f"GPU tensors in a list must share one dtype: {[str(t.dtype) for t in tensors]}")
+        if any(t.device != tensors[0].device for t in tensors):
+            raise ValueError("GPU tensors in a list must live on one device")
+        if any(t.layout != torch.strided for t in tensors):
+            raise TypeError("Sparse GPU tensors are not supported; pass a scipy sparse matrix or a dense tensor")
+        if tensors[0].dtype not in (torch.float32, torch.float64):
+            try:
+                debug = int(self.params.get("verbosity", self.params.get("verbose", 1))) >= 2
+            except (TypeError, ValueError):
+                debug = False
+            if debug:
+                _log_info(f"[Debug] Converting {tensors[0].dtype} GPU tensor data to float32")
+            tensors = [t.to(torch.float32) for t in tensors]
+        dtype = C_API_DTYPE_FLOAT32 if tensors[0].dtype == torch.float32 else C_API_DTYPE_FLOAT64
+        cat_idx = self._resolve_categorical(feature_names, ncol)
+        n = len(tensors)
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.c_void_p(t.data_ptr()) for t in tensors])
+        nrows = (ctypes.c_int32 * n)(*[int(t.shape[0]) for t in tensors])
+        rs = (ctypes.c_int64 * n)(*[int(t.stride(0)) for t in tensors])
+        cs = (ctypes.c_int64 * n)(*[int(t.stride(1)) for t in tensors])
+        with torch.cuda.device(tensors[0].device):
+            # the library works on a stream of its own: the tensors' producer must be done
+            torch.cuda.current_stream().synchronize()
+            _check(_LIB.LGBM_DatasetCreateFromDeviceMats(ctypes.c_int32(n), ptrs, ctypes.c_int(dtype), nrows,
+                                                         ctypes.c_int32(ncol), rs, cs,
+                                                         _c_str(self._build_params(cat_idx)), ref, ctypes.byref(out)))
+
     @staticmethod
     def _indptr(a: np.ndarray):
         if a.dtype == np.int32:
@@ -596,6 +677,7 @@ class Dataset:
                                                           ex.chunks, ctypes.byref(ex.schema)))
             self.version += 1
             return self
+        data = _metadata_to_host(data)
         dtype = _FIELD_TYPES.get(field_name, np.float32)
         if field_name == "init_score":
             arr = np.asarray(data, dtype=np.float64)
@@ -633,6 +715,7 @@ class Dataset:
         return arr
 
     def set_label(self, label: Any) -> "Dataset":
+        label = _metadata_to_host(label)
         self.label = label
         if self.handle is not None and label is not None:
             if pd is not None and isinstance(label, (pd.Series, pd.DataFrame)):
@@ -642,6 +725,7 @@ class Dataset:
         return self
 
     def set_weight(self, weight: Any) -> "Dataset":
+        weight = _metadata_to_host(weight)
         if weight is not None and np.all(np.asarray(weight) == 1):
             weight = None
         self.weight = weight
@@ -651,6 +735,7 @@ class Dataset:
         return self
 
     def set_init_score(self, init_score: Any) -> "Dataset":
+        init_score = _metadata_to_host(init_score)
         self.init_score = init_score
         if self.handle is not None and init_score is not None:
             self.set_field("init_score", init_score)
@@ -658,12 +743,14 @@ class Dataset:
         return self
 
     def set_group(self, group: Any) -> "Dataset":
+        group = _metadata_to_host(group)
         self.group = group
         if self.handle is not None and group is not None:
             self.set_field("group", np.asarray(group, dtype=np.int32))
         return self
 
     def set_position(self, position: Any) -> "Dataset":
+        position = _metadata_to_host(position)
         self.position = position
         if self.handle is not None and position is not None:
             self.set_field("position", np.asarray(position, dtype=np.int32))
@@ -711,6 +798,10 @@ class Dataset:
                     self.data = self.data[self.used_indices]
                 elif _is_arrow(self.data):
                     self.data = self.data.take(self.used_indices)
+                elif _device_tensor_list(self.data) is not None:
+                    self.data = None
+                    raise LightGBMError("Cannot subset the raw rows of a Dataset built from GPU tensors; "
+                                        "construct it with free_raw_data=True, or index the tensor yourself")
                 elif not _is_path(self.data):
                     _log_warning(f"Cannot subset {type(self.data).__name__} type of raw data.\n"
                                  "Returning original raw data")
@@ -751,7 +842,11 @@ class Dataset:
         ``used_indices`` for a subset (reference basic.py ``_set_init_score_by_predictor``)."""
         if data is None:
             return None
-        if _is_path(data):
+        tensors = _device_tensor_list(data)
+        if tensors is not None:
+            # GPU tensors are scored where they lie; raw scores equal predict's bit for bit
+            raw = np.concatenate([predictor.predict_device(t, raw_score=True).cpu().numpy() for t in tensors], axis=0)
+        elif _is_path(data):
             header = str(self.params.get("header", self.params.get("has_header", False))).lower() in ("true", "1")
             raw = predictor.predict(str(data), raw_score=True, data_has_header=header)
         else:

@@ -416,6 +416,43 @@ int LGBM_DatasetCreateFromMats(int32_t nmat, const void** data, int data_type, i
   API_END();
 }
 
+static DatasetHandle BuildFromStridedMats(int32_t nmat, const void** data, int data_type, const int32_t* nrow,
+                                          int32_t ncol, const int64_t* row_stride, const int64_t* col_stride,
+                                          bool on_device, const char* parameters, const DatasetHandle reference) {
+  if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) Log::Fatal("The data must be float32 or float64");
+  if (nmat < 0 || (nmat > 0 && (data == nullptr || nrow == nullptr || row_stride == nullptr || col_stride == nullptr))) {
+    Log::Fatal("The matrix list is incomplete");
+  }
+  std::vector<StridedChunk> chunks(nmat);
+  for (int i = 0; i < nmat; ++i) {
+    chunks[i].data = data[i];
+    chunks[i].nrow = nrow[i];
+    chunks[i].row_stride = row_stride[i];
+    chunks[i].col_stride = col_stride[i];
+  }
+  StridedChunkSource src(std::move(chunks), data_type == C_API_DTYPE_FLOAT64, ncol, on_device);
+  return BuildFromSource(src, parameters, reference);
+}
+
+int LGBM_DatasetCreateFromDeviceMats(int32_t nmat, const void** data, int data_type, const int32_t* nrow, int32_t ncol,
+                                     const int64_t* row_stride, const int64_t* col_stride, const char* parameters,
+                                     const DatasetHandle reference, DatasetHandle* out) {
+  API_BEGIN();
+  if (device::DeviceCount() <= 0) {  // before any pointer is looked at
+    Log::Fatal("Dataset from GPU tensors: no gfx950 GPU is visible to this process; pass host arrays instead");
+  }
+  *out = BuildFromStridedMats(nmat, data, data_type, nrow, ncol, row_stride, col_stride, true, parameters, reference);
+  API_END();
+}
+
+int LGBM_DatasetTestCreateFromSampledMats(int32_t nmat, const void** data, int data_type, const int32_t* nrow,
+                                          int32_t ncol, const int64_t* row_stride, const int64_t* col_stride,
+                                          const char* parameters, const DatasetHandle reference, DatasetHandle* out) {
+  API_BEGIN();
+  *out = BuildFromStridedMats(nmat, data, data_type, nrow, ncol, row_stride, col_stride, false, parameters, reference);
+  API_END();
+}
+
 int LGBM_DatasetCreateFromCSR(const void* indptr, int indptr_type, const int32_t* indices, const void* data,
                               int data_type, int64_t nindptr, int64_t nelem, int64_t num_col, const char* parameters,
                               const DatasetHandle reference, DatasetHandle* out) {

@@ -10,8 +10,10 @@
 #include <omp.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <numeric>
 #include <set>
 
@@ -370,12 +372,86 @@ void Dataset::PushRows(const RowSource& src, data_size_t start_row) {
 
 Dataset::~Dataset() { device::ReleaseDeviceRows(this); }
 
+StridedChunkSource::StridedChunkSource(std::vector<StridedChunk> chunks, bool f64, int ncol, bool on_device)
+    : chunks_(std::move(chunks)), f64_(f64), ncol_(ncol), on_device_(on_device) {
+  if (ncol_ <= 0) Log::Fatal("The data has no columns");
+  int64_t total = 0;
+  for (const auto& c : chunks_) {
+    if (c.nrow < 0 || c.row_stride < 0 || c.col_stride < 0) Log::Fatal("Row counts and strides must not be negative");
+    if (c.nrow > 0 && c.data == nullptr) Log::Fatal("A data chunk is null");
+    starts_.push_back(static_cast<data_size_t>(total));
+    total += c.nrow;
+  }
+  if (total > std::numeric_limits<data_size_t>::max()) Log::Fatal("Too many rows");
+  total_ = static_cast<data_size_t>(total);
+}
+
+void StridedChunkSource::GetRow(data_size_t i, std::vector<std::pair<int, double>>* out) const {
+  if (on_device_) Log::Fatal("Rows of a device-resident matrix cannot be read on the host");
+  const size_t m = std::upper_bound(starts_.begin(), starts_.end(), i) - starts_.begin() - 1;
+  const StridedChunk& c = chunks_[m];
+  const int64_t base = static_cast<int64_t>(i - starts_[m]) * c.row_stride;
+  out->clear();
+  for (int j = 0; j < ncol_; ++j) {
+    const int64_t k = base + j * c.col_stride;
+    const double v = f64_ ? static_cast<const double*>(c.data)[k] : static_cast<const float*>(c.data)[k];
+    if (std::isnan(v) || std::fabs(v) > kZeroThreshold) out->emplace_back(j, v);
+  }
+}
+
+void StridedChunkSource::GatherRows(const int* rows, data_size_t n, void* out) const {
+  if (n <= 0) return;
+  if (on_device_) {
+    device::GatherDeviceRows(chunks_.data(), static_cast<int>(chunks_.size()), f64_, ncol_, rows, 0, n, out);
+    return;
+  }
+  const size_t es = f64_ ? 8 : 4;
+#pragma omp parallel for schedule(static)
+  for (data_size_t s = 0; s < n; ++s) {
+    const data_size_t i = rows[s];
+    const size_t m = std::upper_bound(starts_.begin(), starts_.end(), i) - starts_.begin() - 1;
+    const StridedChunk& c = chunks_[m];
+    const char* src = static_cast<const char*>(c.data);
+    char* dst = static_cast<char*>(out) + static_cast<size_t>(s) * ncol_ * es;
+    const int64_t base = static_cast<int64_t>(i - starts_[m]) * c.row_stride;
+    for (int j = 0; j < ncol_; ++j) std::memcpy(dst + j * es, src + (base + j * c.col_stride) * es, es);
+  }
+}
+
+void StridedChunkSource::CopyToHost(void* out) const {
+  if (on_device_) {
+    device::GatherDeviceRows(chunks_.data(), static_cast<int>(chunks_.size()), f64_, ncol_, nullptr, 0, total_, out);
+    return;
+  }
+  std::vector<int> all(total_);
+  std::iota(all.begin(), all.end(), 0);
+  GatherRows(all.data(), total_, out);
+}
+
 void Dataset::PackRows(const RowSource& src, data_size_t start_row, bool reset) {
   const data_size_t nrows = src.num_rows();
   if (reset) {
     num_data_ = nrows;
     bins_.assign(static_cast<size_t>(num_data_) * row_stride_, 0);
     if (keep_raw_) raw_.assign(static_cast<size_t>(num_data_) * features_.size(), 0.0f);
+  }
+  // a matrix that already lives on the GPU is binned there whatever device_type and
+  // device_binning say; what the device packer does not serve goes through one host copy
+  const auto* strided = dynamic_cast<const StridedChunkSource*>(&src);
+  if (strided != nullptr && strided->on_device()) {
+    if (!reset || start_row != 0) Log::Fatal("Device-resident rows cannot be pushed into a Dataset");
+    std::string why = keep_raw_ ? "linear_tree keeps the raw feature values on the host" : "";
+    if (why.empty() &&
+        device::DevicePackResident(*this, strided->chunks().data(), static_cast<int>(strided->chunks().size()),
+                                   strided->is_f64(), strided->num_cols(), bins_.data(), device_pack_, &why)) {
+      return;
+    }
+    Log::Info("Dataset from GPU tensors: copying the matrix to the host once and binning it there (%s)", why.c_str());
+    std::vector<char> host(static_cast<size_t>(nrows) * strided->num_cols() * (strided->is_f64() ? 8 : 4));
+    strided->CopyToHost(host.data());
+    DenseSource host_rows(host.data(), strided->is_f64(), nrows, strided->num_cols(), true);
+    PackRows(host_rows, 0, false);
+    return;
   }
   // device binning of a dense row-major matrix (bin_kernels.hip); the device rows are kept
   // for the HIP learner. Anything else (sparse / Arrow / streaming / raw values) bins here.
@@ -469,9 +545,22 @@ void Dataset::Construct(const RowSource& src, const Config& cfg, const Dataset* 
   std::vector<std::vector<double>> col_vals(num_total_features_);
   std::vector<std::vector<int>> col_rows(num_total_features_);
   {
+    // strided chunks (device tensors and their host test double) hand the sample over as one
+    // compact matrix, gathered on the device when the chunks live there
+    const auto* strided = dynamic_cast<const StridedChunkSource*>(&src);
+    std::vector<char> compact;
+    std::unique_ptr<DenseSource> sampled;
+    if (strided != nullptr) {
+      ScopedTimer ts("Dataset::GatherSample");
+      compact.resize(sample_idx.size() * static_cast<size_t>(num_total_features_) * (strided->is_f64() ? 8 : 4));
+      strided->GatherRows(sample_idx.data(), static_cast<data_size_t>(sample_idx.size()), compact.data());
+      sampled = std::make_unique<DenseSource>(compact.data(), strided->is_f64(),
+                                              static_cast<data_size_t>(sample_idx.size()), num_total_features_, true);
+    }
     std::vector<std::pair<int, double>> row;
     for (int s = 0; s < static_cast<int>(sample_idx.size()); ++s) {
-      src.GetRow(sample_idx[s], &row);
+      if (sampled) sampled->GetRow(s, &row);
+      else src.GetRow(sample_idx[s], &row);
       for (auto& kv : row) {
         if (kv.first >= num_total_features_) continue;
         col_vals[kv.first].push_back(kv.second);
