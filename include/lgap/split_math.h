@@ -163,6 +163,24 @@ LGAP_HD inline double SplitGain(double lg, double lh, double rg, double rh, cons
 
 LGAP_HD inline int RoundCount(double x) { return static_cast<int>(x + 0.5f); }
 
+// The smallest hessian sum a child may have, given its leaf's total `sum_h`. A child's sum is the
+// total minus the other side's running sum, so it is known only to the rounding of sums of the
+// total's size, and the kEpsilon in each side (2 * kEpsilon in the total), which the reference
+// means to keep every child positive, is absorbed once the total exceeds ~16. A child that holds
+// no hessian at all then comes out as 0 or a few ulps of the total, passes
+// min_sum_hessian_in_leaf = 0, and any residue r in its gradient sum (rounding on the host, the
+// fixed-point histograms' quantisation on the device) gives it the gain r * r / ~0: infinite or
+// huge. Its row count does not stop it: with non-constant hessians that is the total minus the
+// other side's count as estimated bin by bin from the hessians, which can fall short of the
+// total. So a child below 2^-40 of the total (thousands of ulps, far under any row's hessian that
+// could matter to a sum of that size) or below kEpsilon is never taken. With the default
+// min_sum_hessian_in_leaf = 1e-3 this changes nothing below a total of 1e9.
+LGAP_HD inline double MinChildHessian(const SplitParams& p, double sum_h) {
+  double m = p.min_sum_hessian_in_leaf > kEpsilon ? p.min_sum_hessian_in_leaf : kEpsilon;
+  const double noise = sum_h * 0x1p-40;
+  return m > noise ? m : noise;
+}
+
 // ----------------------------------------------------------------------------
 // Sequential numerical scan over one full feature histogram (`hist` = 2*num_bin doubles).
 // `out` must be Reset by the caller; the best of REVERSE / forward passes is kept.
@@ -173,6 +191,7 @@ LGAP_HD inline void ScanNumericalPass(const double* hist, const FeatureScanMeta&
                                       bool na_as_missing, bool* splittable, SplitInfo* out,
                                       const ThresholdBounds* tb = nullptr) {
   const double cnt_factor = num_data / sum_h;
+  const double min_h = MinChildHessian(p, sum_h);
   double best_lg = NAN, best_lh = NAN, best_gain = kMinScore;
   data_size_t best_lc = 0;
   uint32_t best_t = static_cast<uint32_t>(m.num_bin);
@@ -193,11 +212,11 @@ LGAP_HD inline void ScanNumericalPass(const double* hist, const FeatureScanMeta&
       rg += g;
       rh += h;
       rc += RoundCount(h * cnt_factor);
-      if (rc < p.min_data_in_leaf || rh < p.min_sum_hessian_in_leaf) continue;
+      if (rc < p.min_data_in_leaf || rh < min_h) continue;
       const data_size_t lc = num_data - rc;
       if (lc < p.min_data_in_leaf) break;
       const double lh = sum_h - rh;
-      if (lh < p.min_sum_hessian_in_leaf) break;
+      if (lh < min_h) break;
       const double lg = sum_g - rg;
       if (use_rand && t - 1 != m.rand_threshold) continue;
       if (tb != nullptr) {
@@ -231,11 +250,11 @@ LGAP_HD inline void ScanNumericalPass(const double* hist, const FeatureScanMeta&
       lg += g;
       lh += h;
       lc += RoundCount(h * cnt_factor);
-      if (lc < p.min_data_in_leaf || lh < p.min_sum_hessian_in_leaf) continue;
+      if (lc < p.min_data_in_leaf || lh < min_h) continue;
       const data_size_t rc = num_data - lc;
       if (rc < p.min_data_in_leaf) break;
       const double rh = sum_h - lh;
-      if (rh < p.min_sum_hessian_in_leaf) break;
+      if (rh < min_h) break;
       const double rg = sum_g - lg;
       if (use_rand && t != m.rand_threshold) continue;
       const double gain = SplitGain2(lg, lh, rg, rh, p, m.monotone, lc, rc, parent_output, lb, rb);
@@ -321,6 +340,7 @@ LGAP_HD inline bool FindBestCategorical(const double* hist, const FeatureScanMet
   }
   const double min_gain_shift = gain_shift + p.min_gain_to_split;
   const double cnt_factor = num_data / sum_h;
+  const double min_h = MinChildHessian(p, sum_h);
   bool splittable = false;
   double best_gain = kMinScore, best_lg = 0.0, best_lh = 0.0;
   data_size_t best_lc = 0;
@@ -331,11 +351,11 @@ LGAP_HD inline bool FindBestCategorical(const double* hist, const FeatureScanMet
     for (int t = 1; t < m.num_bin; ++t) {
       const double g = hist[2 * t], h = hist[2 * t + 1];
       const data_size_t c = RoundCount(h * cnt_factor);
-      if (c < p.min_data_in_leaf || h < p.min_sum_hessian_in_leaf) continue;
+      if (c < p.min_data_in_leaf || h < min_h) continue;
       const data_size_t oc = num_data - c;
       if (oc < p.min_data_in_leaf) continue;
       const double oh = sum_h - h - kEpsilon;
-      if (oh < p.min_sum_hessian_in_leaf) continue;
+      if (oh < min_h) continue;
       const double og = sum_g - g;
       if (use_rand && t != m.rand_threshold) continue;
       const double gain = SplitGain(og, oh, g, h + kEpsilon, p, 0, oc, c, parent_output, bounds);
@@ -380,11 +400,11 @@ LGAP_HD inline bool FindBestCategorical(const double* hist, const FeatureScanMet
         lh += h;
         lc += c;
         cur_group += c;
-        if (lc < p.min_data_in_leaf || lh < p.min_sum_hessian_in_leaf) continue;
+        if (lc < p.min_data_in_leaf || lh < min_h) continue;
         const data_size_t rc = num_data - lc;
         if (rc < p.min_data_in_leaf || rc < p.min_data_per_group) break;
         const double rh = sum_h - lh;
-        if (rh < p.min_sum_hessian_in_leaf) break;
+        if (rh < min_h) break;
         if (cur_group < p.min_data_per_group) continue;
         cur_group = 0;
         const double rg = sum_g - lg;

@@ -118,6 +118,7 @@ __device__ bool ScanNumericalWave(const SplitParams& p, const DevFeature& fi, co
   const int lane = threadIdx.x & 63;
   const double sum_h = sh_raw + 2 * kEpsilon;
   const double cnt_factor = n / sum_h;
+  const double min_h = MinChildHessian(p, sum_h);
   const double shift = LeafGain(sg, sum_h, p, n, po) + p.min_gain_to_split;
   const int nb = fi.num_bin;
   const bool two_dir = nb > 2 && fi.missing != 0;
@@ -191,8 +192,8 @@ __device__ bool ScanNumericalWave(const SplitParams& p, const DevFeature& fi, co
         const int rc = ec + pc[k];
         const int lc = n - rc;
         const double lh = sum_h - rh;
-        if (rc >= p.min_data_in_leaf && rh >= p.min_sum_hessian_in_leaf && lc >= p.min_data_in_leaf &&
-            lh >= p.min_sum_hessian_in_leaf && (!use_rand || thr == rand_thr)) {
+        if (rc >= p.min_data_in_leaf && rh >= min_h && lc >= p.min_data_in_leaf && lh >= min_h &&
+            (!use_rand || thr == rand_thr)) {
           const double lg = sg - rg;
           const double gain = SplitGain(lg, lh, rg, rh, p, mono, lc, rc, po, bounds);
           if (gain > shift) {
@@ -259,8 +260,8 @@ __device__ bool ScanNumericalWave(const SplitParams& p, const DevFeature& fi, co
           const int lc = ec + pc[k];
           const int rc = n - lc;
           const double rh = sum_h - lh;
-          if (lc >= p.min_data_in_leaf && lh >= p.min_sum_hessian_in_leaf && rc >= p.min_data_in_leaf &&
-              rh >= p.min_sum_hessian_in_leaf && (!use_rand || thr == rand_thr)) {
+          if (lc >= p.min_data_in_leaf && lh >= min_h && rc >= p.min_data_in_leaf && rh >= min_h &&
+              (!use_rand || thr == rand_thr)) {
             const double rg = sg - lg;
             const double gain = SplitGain(lg, lh, rg, rh, p, mono, lc, rc, po, bounds);
             if (gain > shift) {
@@ -333,6 +334,7 @@ __device__ bool ScanCategoricalWave(const SplitParams& p_in, const FeatureScanMe
   }
   const double min_gain_shift = gain_shift + p.min_gain_to_split;
   const double cnt_factor = n / sum_h;
+  const double min_h = MinChildHessian(p, sum_h);
   const bool use_rand = p.extra_trees != 0;
   bool sp = false;
   double best_gain = kMinScore, best_lg = 0.0, best_lh = 0.0;
@@ -345,11 +347,11 @@ __device__ bool ScanCategoricalWave(const SplitParams& p_in, const FeatureScanMe
     for (int t = 1 + lane; t < m.num_bin; t += 64) {
       const double g = H[2 * t], h = H[2 * t + 1];
       const int c = RoundCount(h * cnt_factor);
-      if (c < p.min_data_in_leaf || h < p.min_sum_hessian_in_leaf) continue;
+      if (c < p.min_data_in_leaf || h < min_h) continue;
       const int oc = n - c;
       if (oc < p.min_data_in_leaf) continue;
       const double oh = sum_h - h - kEpsilon;
-      if (oh < p.min_sum_hessian_in_leaf) continue;
+      if (oh < min_h) continue;
       const double og = sum_g - g;
       if (use_rand && t != m.rand_threshold) continue;
       const double gain = SplitGain(og, oh, g, h + kEpsilon, p, 0, oc, c, po, bounds);
@@ -435,11 +437,11 @@ __device__ bool ScanCategoricalWave(const SplitParams& p_in, const FeatureScanMe
           lh += h;
           lc += c;
           cur_group += c;
-          if (lc < p.min_data_in_leaf || lh < p.min_sum_hessian_in_leaf) continue;
+          if (lc < p.min_data_in_leaf || lh < min_h) continue;
           const int rc = n - lc;
           if (rc < p.min_data_in_leaf || rc < p.min_data_per_group) break;
           const double rh = sum_h - lh;
-          if (rh < p.min_sum_hessian_in_leaf) break;
+          if (rh < min_h) break;
           if (cur_group < p.min_data_per_group) continue;
           cur_group = 0;
           const double rg = sum_g - lg;

@@ -499,12 +499,46 @@ void TestEnginePlan() {
   lgap::Log::ResetLevel(level);
 }
 
+// A child that holds no hessian is no split candidate even with min_sum_hessian_in_leaf = 0 and
+// a count estimate that leaves it a row (split_math.h MinChildHessian): bins 0-3 are empty, the
+// per-bin count estimates of bins 4-7 round to 9 of the 10 rows, the total absorbs its
+// 2 * kEpsilon, and the leaf's gradient sum carries a residue.
+void TestScanSkipsChildWithoutHessian() {
+  lgap::SplitParams p;
+  p.min_sum_hessian_in_leaf = 0.0;
+  p.min_data_in_leaf = 1;
+  lgap::FeatureScanMeta m;
+  m.num_bin = 8;
+  const double h[4] = {2.8, 32.4, 32.4, 32.4}, g[4] = {1.5, -20.0, 5.0, 12.0};
+  double hist[16] = {0.0};
+  double sum_g = 1e-5, sum_h = 0.0;
+  for (int b = 3; b >= 0; --b) {  // (summed as the reverse pass does: the same bits)
+    hist[2 * (4 + b)] = g[b];
+    hist[2 * (4 + b) + 1] = h[b];
+    sum_g += g[b];
+    sum_h += h[b];
+  }
+  EXPECT(sum_h + 2 * lgap::kEpsilon == sum_h && lgap::kEpsilon + h[3] == h[3]);
+  // the empty side comes out as exactly 0, and as one and three ulps of the total
+  const double totals[3] = {sum_h, std::nextafter(sum_h, 1e9), std::nextafter(std::nextafter(std::nextafter(sum_h, 1e9), 1e9), 1e9)};
+  for (const double total : totals) {
+    lgap::SplitInfo out;
+    out.Reset();
+    const bool splittable = lgap::FindBestNumerical(hist, m, p, sum_g, total, 10, 0.0, lgap::LeafBounds(), &out);
+    EXPECT(splittable);
+    EXPECT(std::isfinite(out.gain) && out.gain > 0.0 && out.gain < 100.0);
+    EXPECT(out.threshold >= 4u && out.threshold <= 6u);
+    EXPECT(out.left_sum_hessian > 1.0 && out.right_sum_hessian > 1.0);
+  }
+}
+
 int main(int argc, char** argv) {
   const std::string data = argc > 1 ? argv[1] : "tests/data";
   TestEnginePlan();
   TestRandom();
   TestCommon();
   TestPointwiseMetric();
+  TestScanSkipsChildWithoutHessian();
   TestTrainPredictRoundTrip(data);
   TestParallelErrorsReturnMinusOne();
   TestBinPiecesMatchDenseBounds();
