@@ -38,6 +38,8 @@ $(BUILD)/%.hip.o: src/%.hip $(HEADERS)
 # -ffp-contract=fast the backend fuses them whatever the source says (the fp contract pragma in
 # predict_pack.h is honoured only from -ffp-contract=on down), so this object is built without it.
 $(BUILD)/device/predict_kernels.hip.o: HIPFLAGS += -ffp-contract=off
+# the same for predict_contrib_device's weights and sums (contrib_pack.h)
+$(BUILD)/device/contrib_kernels.hip.o: HIPFLAGS += -ffp-contract=off
 
 $(LIB): $(CPP_OBJS) $(HIP_OBJS)
 	@mkdir -p $(OUT)

@@ -173,6 +173,24 @@ LIGHTGBM_C_EXPORT int LGBM_BoosterTestPackedPredict(BoosterHandle handle, const 
                                                     int32_t nrow, int32_t ncol, int predict_type, int start_iteration,
                                                     int num_iteration, const char* parameter, int64_t* out_len,
                                                     double* out_result);
+// SHAP values on the device from a dense row-major matrix (Booster.predict_contrib_device):
+// nrow x trees-per-iteration x (features + 1) doubles, the layout and length of PREDICT_CONTRIB
+// (LGBM_BoosterCalcNumPredict). `data` and `out_result` may each be host memory or memory of the
+// current device. The values equal LGBM_BoosterPredictForMat's to rounding (the sums are
+// associated in another order); the last column of each class block, the expected value, bit for
+// bit. Returns -1, with nothing falling back to the host, for a process without a GPU,
+// pred_early_stop=true, a model with linear trees, and a root-to-leaf path that splits on more
+// than 64 distinct features (kCMaxPathFeatures, src/device/contrib_pack.h).
+LIGHTGBM_C_EXPORT int LGBM_BoosterPredictContribForMatDevice(BoosterHandle handle, const void* data, int data_type,
+                                                             int32_t nrow, int32_t ncol, int start_iteration,
+                                                             int num_iteration, const char* parameter,
+                                                             int data_on_device, int out_on_device, int64_t* out_len,
+                                                             double* out_result);
+// Test hook: the path pack and per-row function of the device path, run in a host loop (no GPU).
+LIGHTGBM_C_EXPORT int LGBM_BoosterTestPackedContrib(BoosterHandle handle, const void* data, int data_type,
+                                                    int32_t nrow, int32_t ncol, int start_iteration,
+                                                    int num_iteration, const char* parameter, int64_t* out_len,
+                                                    double* out_result);
 // A Dataset from dense matrices that already live on the GPU (torch tensors): nmat row chunks of
 // ncol columns, fp32 or fp64, chunk i holding value (r, c) at data[i][r * row_stride[i] +
 // c * col_stride[i]] (strides in elements, so views are read in place). The bin-construction

@@ -1412,34 +1412,7 @@ class Booster:
         if kwargs.pop("pred_contrib", False):
             ptype = C_API_PREDICT_CONTRIB  # refused by the library with its own message
         params = _c_str(param_dict_to_str(kwargs))
-        tensor = None
-        mod = type(data).__module__ or ""
-        if mod == "torch" or mod.startswith("torch."):
-            import torch
-
-            if isinstance(data, torch.Tensor):
-                tensor = data
-        if tensor is not None:
-            import torch
-
-            if not tensor.is_cuda:
-                raise TypeError("predict_device takes a torch tensor on the GPU or a numpy array; "
-                                "pass tensor.numpy() here or to Booster.predict")
-            if tensor.dim() != 2:
-                raise ValueError("Input tensor must be 2 dimensional")
-            if tensor.dtype not in (torch.float32, torch.float64):
-                tensor = tensor.to(torch.float64)
-            tensor = tensor.contiguous()
-            dtype = C_API_DTYPE_FLOAT32 if tensor.dtype == torch.float32 else C_API_DTYPE_FLOAT64
-            nrow, ncol = int(tensor.shape[0]), int(tensor.shape[1])
-            data_ptr = ctypes.c_void_p(tensor.data_ptr())
-        elif isinstance(data, np.ndarray):
-            mat, dtype = _to_float_matrix(data)
-            nrow, ncol = mat.shape
-            data_ptr = mat.ctypes.data_as(ctypes.c_void_p)
-        else:
-            raise TypeError(f"predict_device takes a 2-D numpy array or a torch tensor on the GPU, not "
-                            f"{type(data).__name__}; use Booster.predict for other inputs")
+        tensor, data_ptr, dtype, nrow, ncol, _keep = self._device_matrix(data, "predict_device")
         n_pred = ctypes.c_int64(0)
         _check(_LIB.LGBM_BoosterCalcNumPredict(self.handle, ctypes.c_int(nrow), ctypes.c_int(ptype),
                                                ctypes.c_int(start_iteration), ctypes.c_int(num_iteration),
@@ -1468,6 +1441,83 @@ class Booster:
         if nrow == 0 or (per == 1 and ptype != C_API_PREDICT_LEAF_INDEX):
             return out_t
         return out_t.reshape(nrow, per)
+
+    def predict_contrib_device(self, data: Any, start_iteration: int = 0, num_iteration: Optional[int] = None,
+                               **kwargs: Any) -> Any:
+        """SHAP values (``predict(data, pred_contrib=True)``) computed on the GPU.
+
+        ``data`` is a 2-D numpy array (the result is a numpy float64 array) or a 2-D torch tensor
+        on the GPU (read in place; the result is a float64 tensor on the same device). Either way
+        the shape is ``(nrow, k * (num_features + 1))``, as ``predict`` returns it: per class the
+        features' contributions and, last, the expected value. The expected-value columns equal
+        ``predict``'s bit for bit; the contributions agree to rounding, since the device sums each
+        root-to-leaf path on its own and ``predict`` recurses over the tree. As in ``predict``,
+        nothing is divided by the iteration count for random forests.
+
+        Refused, with nothing falling back to the host: a process without a GPU,
+        ``pred_early_stop``, a root-to-leaf path that splits on more than 64 distinct features, and
+        models with linear trees. ``predict`` ignores the linear leaf coefficients in its SHAP
+        values, so they do not add up to the model's score; the device does not reproduce that.
+        """
+        if num_iteration is None:
+            num_iteration = self.best_iteration if self.best_iteration > 0 else -1
+        params = _c_str(param_dict_to_str(kwargs))
+        tensor, data_ptr, dtype, nrow, ncol, _keep = self._device_matrix(data, "predict_contrib_device")
+        n_pred = ctypes.c_int64(0)
+        _check(_LIB.LGBM_BoosterCalcNumPredict(self.handle, ctypes.c_int(nrow), ctypes.c_int(C_API_PREDICT_CONTRIB),
+                                               ctypes.c_int(start_iteration), ctypes.c_int(num_iteration),
+                                               ctypes.byref(n_pred)))
+        out_len = ctypes.c_int64(0)
+        per = n_pred.value // nrow if nrow > 0 else 0
+        if tensor is None:
+            out = np.empty(n_pred.value, dtype=np.float64)
+            _check(_LIB.LGBM_BoosterPredictContribForMatDevice(
+                self.handle, data_ptr, ctypes.c_int(dtype), ctypes.c_int32(nrow), ctypes.c_int32(ncol),
+                ctypes.c_int(start_iteration), ctypes.c_int(num_iteration), params, ctypes.c_int(0), ctypes.c_int(0),
+                ctypes.byref(out_len), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+            return out.reshape(nrow, per)
+        import torch
+
+        with torch.cuda.device(tensor.device):
+            out_t = torch.empty(n_pred.value, dtype=torch.float64, device=tensor.device)
+            # the library works on a stream of its own: the tensor's producer must be done
+            torch.cuda.current_stream().synchronize()
+            _check(_LIB.LGBM_BoosterPredictContribForMatDevice(
+                self.handle, data_ptr, ctypes.c_int(dtype), ctypes.c_int32(nrow), ctypes.c_int32(ncol),
+                ctypes.c_int(start_iteration), ctypes.c_int(num_iteration), params, ctypes.c_int(1), ctypes.c_int(1),
+                ctypes.byref(out_len),
+                ctypes.cast(ctypes.c_void_p(out_t.data_ptr()), ctypes.POINTER(ctypes.c_double))))
+        return out_t.reshape(nrow, per)
+
+    @staticmethod
+    def _device_matrix(data: Any, who: str):
+        """-> (tensor or None, pointer, C dtype, nrow, ncol, owner of the memory) of predict_device's inputs."""
+        tensor = None
+        mod = type(data).__module__ or ""
+        if mod == "torch" or mod.startswith("torch."):
+            import torch
+
+            if isinstance(data, torch.Tensor):
+                tensor = data
+        if tensor is not None:
+            import torch
+
+            if not tensor.is_cuda:
+                raise TypeError(f"{who} takes a torch tensor on the GPU or a numpy array; "
+                                "pass tensor.numpy() here or to Booster.predict")
+            if tensor.dim() != 2:
+                raise ValueError("Input tensor must be 2 dimensional")
+            if tensor.dtype not in (torch.float32, torch.float64):
+                tensor = tensor.to(torch.float64)
+            tensor = tensor.contiguous()
+            dtype = C_API_DTYPE_FLOAT32 if tensor.dtype == torch.float32 else C_API_DTYPE_FLOAT64
+            return tensor, ctypes.c_void_p(tensor.data_ptr()), dtype, int(tensor.shape[0]), int(tensor.shape[1]), tensor
+        if isinstance(data, np.ndarray):
+            mat, dtype = _to_float_matrix(data)
+            nrow, ncol = mat.shape
+            return None, mat.ctypes.data_as(ctypes.c_void_p), dtype, nrow, ncol, mat
+        raise TypeError(f"{who} takes a 2-D numpy array or a torch tensor on the GPU, not "
+                        f"{type(data).__name__}; use Booster.predict for other inputs")
 
     def _predict_sparse(self, data, ptype, start_iteration, num_iteration, params) -> np.ndarray:
         csr = data.tocsr()

@@ -19,6 +19,8 @@
 #include <string>
 #include <vector>
 
+#include "device/contrib_kernels.h"
+#include "device/contrib_pack.h"
 #include "device/predict_pack.h"
 #include "lgap/arrow.h"
 #include "lgap/boosting.h"
@@ -281,7 +283,8 @@ void PredictPacked(Booster* b, const void* data, int data_type, int32_t nrow, in
   Config pc = ParseConfig(parameter);
   GBDT* g = b->boosting_.get();
   if (predict_type == C_API_PREDICT_CONTRIB) {
-    Log::Fatal("predict_device does not support pred_contrib (SHAP values); use Booster.predict");
+    Log::Fatal("predict_device does not support pred_contrib (SHAP values); use Booster.predict or "
+               "Booster.predict_contrib_device");
   }
   if (pc.pred_early_stop) {
     Log::Fatal("predict_device does not support pred_early_stop; use Booster.predict");
@@ -340,6 +343,35 @@ void PredictPacked(Booster* b, const void* data, int data_type, int32_t nrow, in
       obj->ConvertOutput(raw.data(), o);
     }
   }
+  *out_len = static_cast<int64_t>(nrow) * per_row;
+}
+
+// ---- SHAP values over the path pack (device/contrib_pack.h): the device kernel, or the same
+// per-row function in a host loop (on_device = false, the CPU-only test hook)
+void PredictContribPacked(Booster* b, const void* data, int data_type, int32_t nrow, int32_t ncol, int start_iteration,
+                          int num_iteration, const char* parameter, bool on_device, bool data_on_device,
+                          bool out_on_device, int64_t* out_len, double* out) {
+  std::shared_lock<std::shared_mutex> lk(b->mu_);
+  Config pc = ParseConfig(parameter);
+  GBDT* g = b->boosting_.get();
+  if (pc.pred_early_stop) {
+    Log::Fatal("predict_contrib_device does not support pred_early_stop; use Booster.predict");
+  }
+  g->InitPredict(start_iteration, num_iteration, true);
+  const int per_row = g->NumPredictOneRow(start_iteration, num_iteration, false, true);
+  if (!pc.predict_disable_shape_check && ncol != g->MaxFeatureIdx() + 1 && ncol > 0) {
+    Log::Fatal("The number of features in data (%d) is not the same as it was in training data (%d).\n"
+               "You can set ``predict_disable_shape_check=true`` to discard this error, but please be aware what you are doing.",
+               ncol, g->MaxFeatureIdx() + 1);
+  }
+  const device::ContribPack pack = device::PackContrib(*g, start_iteration, num_iteration);
+  if (per_row != device::ContribWidth(pack.View())) {
+    Log::Fatal("predict_contrib_device: the model returns %d values per row, the pack %d; use Booster.predict", per_row,
+               device::ContribWidth(pack.View()));
+  }
+  const bool f64 = data_type == C_API_DTYPE_FLOAT64;
+  if (!on_device) device::ContribPackedHost(pack, data, f64, nrow, ncol, out);
+  else device::PredictContribDense(pack, data, f64, nrow, ncol, data_on_device, out_on_device, out);
   *out_len = static_cast<int64_t>(nrow) * per_row;
 }
 
@@ -1156,6 +1188,25 @@ int LGBM_BoosterTestPackedPredict(BoosterHandle handle, const void* data, int da
   API_BEGIN();
   PredictPacked(B(handle), data, data_type, nrow, ncol, predict_type, start_iteration, num_iteration, parameter, false,
                 false, false, out_len, out_result);
+  API_END();
+}
+
+int LGBM_BoosterPredictContribForMatDevice(BoosterHandle handle, const void* data, int data_type, int32_t nrow,
+                                           int32_t ncol, int start_iteration, int num_iteration, const char* parameter,
+                                           int data_on_device, int out_on_device, int64_t* out_len,
+                                           double* out_result) {
+  API_BEGIN();
+  PredictContribPacked(B(handle), data, data_type, nrow, ncol, start_iteration, num_iteration, parameter, true,
+                       data_on_device != 0, out_on_device != 0, out_len, out_result);
+  API_END();
+}
+
+int LGBM_BoosterTestPackedContrib(BoosterHandle handle, const void* data, int data_type, int32_t nrow, int32_t ncol,
+                                  int start_iteration, int num_iteration, const char* parameter, int64_t* out_len,
+                                  double* out_result) {
+  API_BEGIN();
+  PredictContribPacked(B(handle), data, data_type, nrow, ncol, start_iteration, num_iteration, parameter, false, false,
+                       false, out_len, out_result);
   API_END();
 }
 
