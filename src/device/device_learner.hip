@@ -122,14 +122,14 @@ namespace {
 // tile budget), quant_lds32 (0 | 1), part_iters (4 | 8 | 16), hist_il (0 | 1), nibble (0: 8-bit
 // rows), quant_hist (off: float histograms under quantized training), scan_global (1), scan_wave
 // (1: the wave-per-item scan below its 64-feature threshold), oob_rows (2 | 4 | 8: rows per
-// thread of the out-of-bag walk). Returns
+// thread of the out-of-bag walk), part_grid (cap of the frontier partition's grid). Returns
 // the key's value, nullptr when it is not set. Read at each use: tests change the environment
 // between trainings in one process. Each key's value has its own storage (a caller may hold the
 // values of several keys at once); empty items (a trailing comma) are skipped.
 const char* KernelOverride(const char* key) {
   static const char* const kKeys[] = {"fhist_threads", "hist_lds_kb", "quant_lds32", "part_iters",
                                       "hist_il",       "nibble",      "quant_hist",  "scan_global",
-                                      "scan_wave",     "oob_rows",    "select_merge"};
+                                      "scan_wave",     "oob_rows",    "select_merge", "part_grid"};
   constexpr int kNumKeys = static_cast<int>(sizeof(kKeys) / sizeof(kKeys[0]));
   thread_local std::string vals[kNumKeys];
   const char* e = std::getenv("LGAP_KERNEL");
@@ -1912,7 +1912,9 @@ class DeviceTreeLearner : public TreeLearner {
       fvrows_.Resize(2 * K * static_cast<size_t>(topk_) * 2 * max_bin_);
     }
     // frontier tile rows: the chain's rows per thread (8192-row tiles were an A/B loss: 10M 400.9
-    // vs 408.9 it/s, 1.25M 746 vs 878; profiles/r05/ab_partition_8192_tiles.log)
+    // vs 408.9 it/s, 1.25M 746 vs 878; profiles/r05/ab_partition_8192_tiles.log). The partition
+    // is not bandwidth-bound: it moves 1.3-2.1 TB/s, and its time followed the instructions per
+    // row and the dependent steps per block, not the bytes (profiles/partition_passes.md).
     fpart_iters_ = part_iters_;
     fpart_tile_ = kPartThreads * fpart_iters_;
     ftile_cap_ = DivUp(N_, fpart_tile_) + fkmax_ + 1;
@@ -1920,12 +1922,18 @@ class DeviceTreeLearner : public TreeLearner {
     ftile_pub_.Zero(stream_);
     for (int i = 3; i < kFrontierIdx; ++i) idx_[i].Resize(std::max(N_, 1));
     // partition grid: the resident blocks (at most one per tile of the tile capacity); a block
-    // takes tiles b, b + G, ... in passes and only waits on lower tiles. A grid of the full tile
-    // capacity (2.4K blocks at 10M) left ~1.2K blocks with no tile in a typical round, dispatched
-    // behind the working ones: each still read the round state before exiting, at the kernel's tail.
+    // takes tiles b, b + G, ..., counts them all and then scatters them, and only waits on lower
+    // tiles. A grid of the full tile capacity (2.4K blocks at 10M) left ~1.2K blocks with no tile
+    // in a typical round, dispatched behind the working ones: each still read the round state
+    // before exiting, at the kernel's tail. LGAP_KERNEL=part_grid=<blocks> caps the grid (tests and
+    // A/B: the only way to make a block own many tiles at small row counts).
     {
       const int per_cu = std::max(1, FrontierPartitionBlocksPerCU(fpart_iters_));
       fpart_grid_ = std::max(1, std::min(ftile_cap_, per_cu * num_cu_));
+      if (const char* e = KernelOverride("part_grid")) {
+        const int v = std::atoi(e);
+        if (v >= 1) fpart_grid_ = std::min(fpart_grid_, v);
+      }
     }
     fscan_lds_ = FrontierScanLds(max_bin_, has_cat_ ? max_cat_bin_ : 1);
     FrontierSetLds(FrontierHistLds(), fscan_lds_, use_dp_, width_);
@@ -2535,14 +2543,15 @@ class DeviceTreeLearner : public TreeLearner {
       }
       std::fprintf(stderr, "fstamps %s (%d rounds, us from block-0 start; t7 = last block exit):%s\n", names[k], cnt,
                    line.c_str());
-      if (at(0, k, 0)) {
-        // the root round alone (the largest histogram / partition of the tree)
+      // the largest round alone: the root's histogram / scan / select, the partition of the root's rows
+      const int r0 = k == 0 ? 1 : 0;
+      if (at(r0, k, 0)) {
         std::string root;
         for (int i = 1; i < kFStampSlots; ++i) {
-          const unsigned long long v = at(0, k, i);
-          if (v >= at(0, k, 0) && v) root += " t" + std::to_string(i) + "=" + common::FormatG((v - at(0, k, 0)) * 0.01);
+          const unsigned long long v = at(r0, k, i);
+          if (v >= at(r0, k, 0) && v) root += " t" + std::to_string(i) + "=" + common::FormatG((v - at(r0, k, 0)) * 0.01);
         }
-        std::fprintf(stderr, "fstamps %s root round:%s\n", names[k], root.c_str());
+        std::fprintf(stderr, "fstamps %s %s:%s\n", names[k], k == 0 ? "first split" : "root round", root.c_str());
       }
     }
     double gap[4] = {0};

@@ -390,7 +390,7 @@ void LaunchFrontierSelect(const FArgs& a, hipStream_t s);
 // final leaves' rows marked for the features on their paths
 void LaunchFrontierLazyCounts(const FArgs& a, hipStream_t s);
 void LaunchFrontierLazyMark(const FArgs& a, hipStream_t s);
-void LaunchFrontierPartition(const FArgs& a, int iters, int grid, hipStream_t s);  // one block per tile
+void LaunchFrontierPartition(const FArgs& a, int iters, int grid, hipStream_t s);  // block b: tiles b, b + grid, ...
 int FrontierPartitionBlocksPerCU(int iters);
 // voting parallel: local top-k per child (after the local-pass k_f_scan), election and
 // packing of the elected features' local rows (after the vote all-gather), global pass over

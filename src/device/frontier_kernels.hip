@@ -2,7 +2,7 @@
 //
 // Launch shapes (fixed per learner; the work of a round is read on the device):
 //   k_f_init        1 x 256
-//   k_f_partition   grid x 256 (contiguous tiles in block order: no co-residency needed)
+//   k_f_partition   grid x 256 (block b takes tiles b, b + grid, ...: no co-residency needed)
 //   k_f_hist        max(hist_grid, ceil(hist_grid / 2) + kmax) x LDS tiles, 512 or 1024 threads
 //                   (1024 for single-tile rows at >= 4M rows: the 10M headline)
 //   k_f_reduce      (2 or 4) x CUs x 256 (grid-stride over (expansion, bin chunk, row group))
@@ -1505,12 +1505,16 @@ __global__ __launch_bounds__(kFScanWaves * 64) void k_f_scan_w(FArgs a) {
 // k_f_partition: stable 2-way partition of every expanded parent (reference
 // data_partition.hpp:101 / cuda_data_partition.cu:290-937, as one launch).
 // Tiles of all expansions are numbered globally ([tile0_e, tile0_e + ntiles_e) for expansion e);
-// block b owns the MAXT contiguous tiles [b MAXT, b MAXT + MAXT). A block counts its tiles,
-// publishes each count, finds the exclusive left-count prefix of its first tile by a decoupled
-// look-back over the earlier tiles OF ITS EXPANSION, publishes its tiles' inclusive prefixes and
-// scatters: lefts go to the front of the parent's range in order, rights fill it from the end.
-// The block that scatters an expansion's last tile knows its total left count and writes the two
-// children (post-split bookkeeping of serial_tree_learner.cpp:766-922).
+// block b of a grid of G owns the tiles b, b + G, b + 2G, ... A block first COUNTS its tiles
+// (kFPartChunk at a time): row ids and column bins of one tile after the other with no barrier
+// and no wait on another block in between, only each row's left bit kept (in LDS), every tile's
+// left count published as soon as its four waves have it. Only then, tile by tile, it finds the
+// tile's exclusive left-count prefix by a decoupled look-back over the earlier tiles OF ITS
+// EXPANSION (by then they have published, whoever owns them), publishes the inclusive prefix,
+// gets the row ids again (lines this block has just loaded; the chunk's first tile keeps them
+// in registers) and scatters: lefts go to the front of the parent's range in order, rights fill
+// it from the end. The block that scatters an expansion's last tile knows its total left count
+// and writes the two children (post-split bookkeeping of serial_tree_learner.cpp:766-922).
 
 // tile granule {epoch:32 | inclusive:1 | value:31}: a tile's left count, or (inclusive) the left
 // count of its expansion's tiles up to and including it
@@ -1537,18 +1541,20 @@ __device__ __forceinline__ bool FGoLeft(const FExp& x, const uint32_t* bits, uin
 constexpr unsigned kLookbackSpins = 2048;  // s_sleep(1) polls (~100 us) before a tile is counted here
 
 constexpr int kLookbackPer = 4;  // predecessors per thread and window (1,024 per window)
+constexpr int kLookbackList = 64;  // unpublished predecessors the block counts per turn of the rare path
 
 struct FLookbackLds {
-  int near, nmiss, list[256 * kLookbackPer], val[256 * kLookbackPer], red[4];
+  int near, nmiss, list[kLookbackList], val[kLookbackList], red[4];
 };
 
 // Exclusive left-count prefix of tile i of expansion x (block-cooperative): windows of
 // kLookbackPer x blockDim predecessors, nearest first, their granules loaded in one round; a window
-// holding an inclusive granule ends the walk. Blocks own contiguous tiles, so a block only waits on
-// LOWER blocks. A predecessor still unpublished after the poll bound (its block not running:
-// nothing here assumes co-residency or dispatch order) is counted by this block -- the same pure
-// function of the tile's rows its owner evaluates -- and published (the identical value). The
-// part_selfcount test hook counts every predecessor here.
+// holding an inclusive granule ends the walk. A block publishes the counts of all its tiles before
+// its first look-back, so the wait on another block is bounded by that block's counting, never by
+// a look-back of its own. A predecessor still unpublished after the poll bound (its block not
+// running: nothing here assumes co-residency or dispatch order) is counted by this block -- the
+// same pure function of the tile's rows its owner evaluates -- and published (the identical
+// value), kLookbackList of them per turn. The part_selfcount test hook counts every predecessor here.
 __device__ int FLookback(const FArgs& a, const FExp& x, const uint32_t* bits, int i, unsigned epoch, FLookbackLds* L) {
   const int t = threadIdx.x;
   const int nt = static_cast<int>(blockDim.x);
@@ -1579,15 +1585,24 @@ __device__ int FLookback(const FArgs& a, const FExp& x, const uint32_t* bits, in
       }
       have[u] = static_cast<unsigned>(v[u] >> 32) == epoch && !a.part_selfcount;
     }
-    __syncthreads();
+    for (;;) {
+      __syncthreads();  // (nmiss zeroed)
+      int slot[kLookbackPer];
 #pragma unroll
-    for (int u = 0; u < kLookbackPer; ++u) {
-      const int j = hi - 1 - (u * nt + t);
-      if (j >= lo && !have[u]) L->list[atomicAdd(&L->nmiss, 1)] = j;
-    }
-    __syncthreads();
-    const int nm = L->nmiss;
-    if (nm > 0) {
+      for (int u = 0; u < kLookbackPer; ++u) {
+        const int j = hi - 1 - (u * nt + t);
+        slot[u] = -1;
+        if (j >= lo && !have[u]) {
+          const int m = atomicAdd(&L->nmiss, 1);
+          if (m < kLookbackList) {
+            L->list[m] = j;
+            slot[u] = m;
+          }
+        }
+      }
+      __syncthreads();
+      const int nm = min(L->nmiss, kLookbackList);
+      if (nm == 0) break;
       // rare: count the unpublished predecessors with the whole block, one tile at a time
       for (int m = 0; m < nm; ++m) {
         const int tile = L->list[m];
@@ -1599,19 +1614,20 @@ __device__ int FLookback(const FArgs& a, const FExp& x, const uint32_t* bits, in
         }
         cc = BlockSumInt(cc, L->red);
         if (t == 0) {
-          L->val[hi - 1 - tile] = cc;
+          L->val[m] = cc;
           FPublish(&a.tile_pub[tile], epoch, cc, false);
         }
       }
       __syncthreads();
 #pragma unroll
       for (int u = 0; u < kLookbackPer; ++u) {
-        const int j = hi - 1 - (u * nt + t);
-        if (j >= lo && !have[u]) {
-          v[u] = static_cast<unsigned long long>(static_cast<unsigned>(L->val[u * nt + t]));  // (an aggregate)
+        if (slot[u] >= 0) {
+          v[u] = static_cast<unsigned long long>(static_cast<unsigned>(L->val[slot[u]]));  // (an aggregate)
           have[u] = true;
         }
       }
+      __syncthreads();  // (list / val / nmiss read by everyone)
+      if (t == 0) L->nmiss = 0;
     }
 #pragma unroll
     for (int u = 0; u < kLookbackPer; ++u) {
@@ -1715,33 +1731,30 @@ __device__ void FPostSplit(const FArgs& a, int e, const FExp& x, int lc) {
   xo->h_count = left_smaller ? lc : rc;
 }
 
-// block sums of M values at once (one barrier pair for all of them)
-template <int M>
-__device__ __forceinline__ void BlockSumMulti(int* v, int* sh) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int m = 0; m < M; ++m) v[m] = WaveSum(v[m]);
-  __syncthreads();  // sh is reused
-  if (lane == 0) {
-#pragma unroll
-    for (int m = 0; m < M; ++m) sh[m * 4 + w] = v[m];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int m = 0; m < M; ++m) v[m] = sh[m * 4] + sh[m * 4 + 1] + sh[m * 4 + 2] + sh[m * 4 + 3];
-}
+// tiles a block counts before it scatters them (the learner's grid leaves a block at most this
+// many at the headline shape; a block that owns more takes them in chunks)
+constexpr int kFPartChunk = 4;
 
-template <int ITERS, int MAXT>
+template <int ITERS>
 __global__ __launch_bounds__(kFPartThreads) __attribute__((amdgpu_waves_per_eu(ITERS == 8 ? 5 : 1))) void k_f_partition(FArgs a) {
   static_assert(kFPartThreads == 256, "4 waves per block");
-  static_assert(MAXT * ITERS <= 32, "left / valid bits of a thread fit one word");
+  static_assert(ITERS <= 32, "the left bits of a thread's rows of one tile fit one word");
   constexpr int kTile = kFPartThreads * ITERS;
+  constexpr int C = kFPartChunk;
+  constexpr int kWaves = kFPartThreads / 64;
+  static_assert(ITERS * kWaves <= 64, "one wave scans a tile's per-(row slot, wave) left counts");
+  // from 8 rows per thread up, 8-bit group bins are split through a 256-bit table of the predicate
+  // (each wave builds its own, 4 evaluations per lane, when the expansion changes) instead of
+  // one evaluation per row
+  constexpr bool kLut = ITERS >= 8;
   __shared__ int s_t0[kFrontierKmax + 1];
   __shared__ FExp s_x[kFrontierKmax];
   __shared__ uint32_t s_bits[kFrontierKmax][kMaxCatWords];
-  __shared__ int sh[MAXT * 4];
-  __shared__ int s_wl[MAXT][ITERS][kFPartThreads / 64];
-  __shared__ int s_wv[MAXT][ITERS][kFPartThreads / 64];
+  __shared__ unsigned s_cnt[C];  // per tile of the chunk: waves arrived << 24 | lefts so far
+  __shared__ int s_ex[C];        // the chunk's expansions
+  __shared__ int s_wl[C][ITERS * kWaves];  // lefts of (row slot i, wave w) at [i * kWaves + w]; then their exclusive scan
+  __shared__ uint32_t s_mask[C][kFPartThreads];  // bit i: the thread's row i of the tile goes left
+  __shared__ uint32_t s_lut[kWaves][8];
   __shared__ FLookbackLds s_lb;
   const FState* stp = a.st;
   if (stp->done) return;
@@ -1751,13 +1764,14 @@ __global__ __launch_bounds__(kFPartThreads) __attribute__((amdgpu_waves_per_eu(I
   FStamp(a, rnd, kFStampPart, 0);
   const int G = static_cast<int>(gridDim.x);
   const int t = threadIdx.x;
-  if (static_cast<int>(blockIdx.x) * MAXT >= T) return;
+  if (static_cast<int>(blockIdx.x) >= T) return;
   // the round's expansions (dword-parallel copy) and their categorical sets
   constexpr int kXWords = static_cast<int>(sizeof(FExp) / 4);
   for (int i = t; i < k * kXWords; i += blockDim.x) {
     reinterpret_cast<uint32_t*>(s_x)[i] = reinterpret_cast<const uint32_t*>(a.exps)[i];
   }
   for (int i = t; i < k * kMaxCatWords; i += blockDim.x) s_bits[i / kMaxCatWords][i % kMaxCatWords] = a.exp_bits[i];
+  if (t < C) s_cnt[t] = 0u;
   __syncthreads();
   if (t <= k) s_t0[t] = t < k ? s_x[t].tile0 : T;
   __syncthreads();
@@ -1768,126 +1782,150 @@ __global__ __launch_bounds__(kFPartThreads) __attribute__((amdgpu_waves_per_eu(I
       if (s_t0[mid] <= tile) lo = mid;
       else hi = mid - 1;
     }
-    return lo;
+    return __builtin_amdgcn_readfirstlane(lo);
   };
-  auto go_left = [&](int e, uint32_t gb) { return FGoLeft(s_x[e], s_bits[e], gb); };
+  // row ids of a tile (-1: past the expansion's rows)
+  auto load_ids = [&](int e, int tile, int (&r)[ITERS]) {
+    const FExp& x = s_x[e];
+    const int pos0 = (tile - x.tile0) * kTile + t;
+    const int cnt = x.count, start = x.start;
+    const int* src = x.src_buf < 0 ? nullptr : a.idx[x.src_buf] + start;
+#pragma unroll
+    for (int i = 0; i < ITERS; ++i) {
+      const int pos = pos0 + i * kFPartThreads;
+      r[i] = pos < cnt ? (src ? src[pos] : start + pos) : -1;
+    }
+  };
   FStamp(a, rnd, kFStampPart, 1);
   const int lane = t & 63, w = t >> 6;
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  // passes of G * MAXT tiles (one pass whenever the grid covers the tile capacity, as the learner
-  // sizes it)
-  for (int bid = static_cast<int>(blockIdx.x) * MAXT; bid < T; bid += G * MAXT) {
-    // ---- counts of the block's tiles (loads issued together: row ids, then bins)
-    int ex[MAXT], rows[MAXT][ITERS];
-    unsigned lbits = 0u, vbits = 0u;  // bit j * ITERS + i: row valid / goes left
-#pragma unroll
-    for (int j = 0; j < MAXT; ++j) {
-      const int tile = bid + j;
-      ex[j] = tile < T ? find(tile) : -1;
-      const int e = ex[j] < 0 ? 0 : ex[j];
+  const bool narrow = a.width == 1;
+  int e_lut = -1;  // the expansion this wave's table describes
+  for (int bid = static_cast<int>(blockIdx.x); bid < T; bid += G * C) {
+    // ---- phase 1, counts: per tile the row ids, then their bins, the next tile's ids in flight
+    // behind them; nothing here waits on a barrier or on another block. The wave that adds a
+    // tile's last partial count publishes it (a tile that starts its expansion: as inclusive).
+    int rows0[ITERS], cur[ITERS];
+    int e = find(bid);
+    load_ids(e, bid, cur);
+#pragma unroll 1
+    for (int c = 0; c < C; ++c) {
+      const int tile = bid + c * G;
+      if (tile >= T) break;
       const FExp& x = s_x[e];
-      const int pos0 = (tile - x.tile0) * kTile + t;
+      uint32_t gb[ITERS];
+      if (narrow) {
+        const uint8_t* col = a.colbins + static_cast<size_t>(x.group) * a.N;
+#pragma unroll
+        for (int i = 0; i < ITERS; ++i) gb[i] = col[static_cast<uint32_t>(max(cur[i], 0))];
+      } else {
+        const uint16_t* col = reinterpret_cast<const uint16_t*>(a.colbins) + static_cast<size_t>(x.group) * a.N;
+#pragma unroll
+        for (int i = 0; i < ITERS; ++i) gb[i] = col[static_cast<uint32_t>(max(cur[i], 0))];
+      }
+      int nxt[ITERS];
+      int e_n = e;
+      if (c + 1 < C && tile + G < T) {
+        e_n = find(tile + G);
+        load_ids(e_n, tile + G, nxt);
+      } else {
+#pragma unroll
+        for (int i = 0; i < ITERS; ++i) nxt[i] = -1;
+      }
+      const bool lut = kLut && narrow;
+      if (lut && e != e_lut) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the last tile's reads of the table)
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const unsigned long long bal = __ballot(FGoLeft(x, s_bits[e], static_cast<uint32_t>(lane + 64 * j)));
+          if (lane == 0) {
+            s_lut[w][2 * j] = static_cast<uint32_t>(bal);
+            s_lut[w][2 * j + 1] = static_cast<uint32_t>(bal >> 32);
+          }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        e_lut = e;
+      }
+      int wcnt = 0;
+      uint32_t m = 0u;
 #pragma unroll
       for (int i = 0; i < ITERS; ++i) {
-        const int pos = pos0 + i * kFPartThreads;
-        rows[j][i] = (ex[j] >= 0 && pos < x.count) ? FRowAt(a, x.src_buf, x.start + pos) : -1;
+        bool left;
+        if (lut) left = (s_lut[w][(gb[i] >> 5) & 7u] >> (gb[i] & 31u)) & 1u;
+        else left = FGoLeft(x, s_bits[e], gb[i]);
+        left = left && cur[i] >= 0;
+        const int nl = __popcll(__ballot(left));
+        if (lane == 0) s_wl[c][i * kWaves + w] = nl;
+        wcnt += nl;
+        m |= (left ? 1u : 0u) << i;
       }
-    }
-    int cnt[MAXT];
-    {
-      uint32_t gb[MAXT][ITERS];
-#pragma unroll
-      for (int j = 0; j < MAXT; ++j) {
-        const int g = s_x[ex[j] < 0 ? 0 : ex[j]].group;
-#pragma unroll
-        for (int i = 0; i < ITERS; ++i) gb[j][i] = rows[j][i] >= 0 ? FColBin(a, g, rows[j][i]) : 0u;
-      }
-#pragma unroll
-      for (int j = 0; j < MAXT; ++j) {
-        cnt[j] = 0;
-#pragma unroll
-        for (int i = 0; i < ITERS; ++i) {
-          const bool valid = rows[j][i] >= 0;
-          const bool left = valid && go_left(ex[j], gb[j][i]);
-          vbits |= (valid ? 1u : 0u) << (j * ITERS + i);
-          lbits |= (left ? 1u : 0u) << (j * ITERS + i);
-          cnt[j] += left ? 1 : 0;
+      s_mask[c][t] = m;
+      if (lane == 0) {
+        const unsigned old = atomicAdd(&s_cnt[c], static_cast<unsigned>(wcnt) | (1u << 24));
+        if ((old >> 24) == kWaves - 1) {
+          FPublish(&a.tile_pub[tile], epoch, static_cast<int>(old & 0xffffffu) + wcnt, tile == x.tile0);
         }
       }
-    }
-    BlockSumMulti<MAXT>(cnt, sh);
-    // aggregates first (a tile that starts its expansion publishes its count as inclusive)
-    if (t == 0) {
-#pragma unroll
-      for (int j = 0; j < MAXT; ++j) {
-        if (ex[j] >= 0) FPublish(&a.tile_pub[bid + j], epoch, cnt[j], bid + j == s_x[ex[j]].tile0);
-      }
-    }
-    FStamp(a, rnd, kFStampPart, 2);
-    // ---- exclusive prefixes: a look-back for the block's first tile only (a later tile of the
-    // block continues its predecessor's expansion, or is the first tile of the next one)
-    int lb[MAXT];
-    lb[0] = ex[0] >= 0 && bid > s_x[ex[0]].tile0 ? FLookback(a, s_x[ex[0]], s_bits[ex[0]], bid, epoch, &s_lb) : 0;
-#pragma unroll
-    for (int j = 1; j < MAXT; ++j) lb[j] = ex[j] >= 0 && ex[j] == ex[j - 1] ? lb[j - 1] + cnt[j - 1] : 0;
-    if (t == 0) {
-#pragma unroll
-      for (int j = 0; j < MAXT; ++j) {
-        if (ex[j] >= 0 && bid + j > s_x[ex[j]].tile0) FPublish(&a.tile_pub[bid + j], epoch, lb[j] + cnt[j], true);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < MAXT; ++j) {
+      if (t == 0) s_ex[c] = e;
 #pragma unroll
       for (int i = 0; i < ITERS; ++i) {
-        const unsigned long long ml = __ballot((lbits >> (j * ITERS + i)) & 1u);
-        const unsigned long long mv = __ballot((vbits >> (j * ITERS + i)) & 1u);
-        if (lane == 0) {
-          s_wl[j][i][w] = __popcll(ml);
-          s_wv[j][i][w] = __popcll(mv);
-        }
+        if (c == 0) rows0[i] = cur[i];
+        cur[i] = nxt[i];
       }
+      e = e_n;
+    }
+    __syncthreads();  // (the waves' left counts and the tiles' totals)
+    // exclusive scan of each tile's ITERS x kWaves left counts in row order (slot, wave): one wave per tile
+    for (int c = w; c < C && bid + c * G < T; c += kWaves) {
+      const int v = lane < ITERS * kWaves ? s_wl[c][lane] : 0;
+      const int incl = WaveInclusiveSumDpp(v);
+      if (lane < ITERS * kWaves) s_wl[c][lane] = incl - v;
     }
     __syncthreads();
-    // ---- scatter
-#pragma unroll
-    for (int j = 0; j < MAXT; ++j) {
-      if (ex[j] < 0) continue;
-      const int e = ex[j];
-      const FExp& x = s_x[e];
-      const int tile = bid + j;
+    FStamp(a, rnd, kFStampPart, 2);
+    // ---- phase 2, tile by tile: exclusive prefix (look-back over the expansion's earlier tiles,
+    // all counted and published in their owners' phase 1), inclusive prefix out, scatter
+#pragma unroll 1
+    for (int c = 0; c < C; ++c) {
+      const int tile = bid + c * G;
+      if (tile >= T) break;
+      const int ec = __builtin_amdgcn_readfirstlane(s_ex[c]);
+      const FExp& x = s_x[ec];
       const int tt = tile - x.tile0;
-      int lbase = lb[j];
-      int rbase = tt * kTile - lbase;
+      // the row ids again, issued ahead of the look-back (the chunk's first tile kept them)
+      int rows[ITERS];
+      if (c == 0) {
+#pragma unroll
+        for (int i = 0; i < ITERS; ++i) rows[i] = rows0[i];
+      } else {
+        load_ids(ec, tile, rows);
+      }
+      const int lb = tt > 0 ? FLookback(a, x, s_bits[ec], tile, epoch, &s_lb) : 0;
+      const int lend = lb + static_cast<int>(s_cnt[c] & 0xffffffu);  // lefts up to and including this tile
+      if (t == 0 && tt > 0) FPublish(&a.tile_pub[tile], epoch, lend, true);
+      const uint32_t m = s_mask[c][t];
       int* out = a.idx[x.dst_buf] + x.start;
+      const int last = x.count - 1;
+      // a row at position p of its expansion with rl lefts before it goes to rl (left) or, from
+      // the end, to the number of rights before it: p - rl
 #pragma unroll
       for (int i = 0; i < ITERS; ++i) {
-        const bool valid = (vbits >> (j * ITERS + i)) & 1u;
-        const bool left = (lbits >> (j * ITERS + i)) & 1u;
+        const bool left = (m >> i) & 1u;
         const unsigned long long ml = __ballot(left);
-        const unsigned long long mv = __ballot(valid);
-        int pl = 0, pv = 0, tl = 0, tv = 0;
-#pragma unroll
-        for (int q = 0; q < kFPartThreads / 64; ++q) {
-          if (q < w) {
-            pl += s_wl[j][i][q];
-            pv += s_wv[j][i][q];
-          }
-          tl += s_wl[j][i][q];
-          tv += s_wv[j][i][q];
-        }
-        if (valid) {
-          const int rl = pl + __popcll(ml & lt_mask);
-          const int rv = pv + __popcll(mv & lt_mask);
-          int* dst = left ? out + lbase + rl : out + (x.count - 1 - (rbase + (rv - rl)));
-          *dst = rows[j][i];
-        }
-        lbase += tl;
-        rbase += tv - tl;
+        const int rl = lb + s_wl[c][i * kWaves + w] + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
+                           static_cast<uint32_t>(ml >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(ml), 0u)));
+        const int p = tt * kTile + i * kFPartThreads + t;
+        if (rows[i] >= 0) out[left ? rl : last - (p - rl)] = rows[i];
       }
-      if (tt == x.ntiles - 1 && t == 0) FPostSplit(a, e, x, lbase);
+      if (tt == x.ntiles - 1 && t == 0) FPostSplit(a, ec, x, lend);
     }
-    __syncthreads();  // (LDS ballot counts reused by the next pass)
+    if (bid + G * C < T) {
+      // (rare: the block owns more tiles than one chunk) the chunk's LDS arrays are reused
+      __syncthreads();
+      if (t < C) s_cnt[t] = 0u;
+      __syncthreads();
+    }
   }
   FStamp(a, rnd, kFStampPart, 3);
   FStampEnd(a, rnd, kFStampPart);
@@ -4268,19 +4306,19 @@ void LaunchFrontierXSelfTest(const FArgs& a, int round, int nvals, unsigned* err
 // resident k_f_partition blocks per CU (occupancy of the instantiation the learner launches)
 int FrontierPartitionBlocksPerCU(int iters) {
   int per_cu = 0;
-  const void* fn = iters == 4    ? reinterpret_cast<const void*>(k_f_partition<4, 1>)
-                   : iters == 16 ? reinterpret_cast<const void*>(k_f_partition<16, 1>)
-                                 : reinterpret_cast<const void*>(k_f_partition<8, 1>);
+  const void* fn = iters == 4    ? reinterpret_cast<const void*>(k_f_partition<4>)
+                   : iters == 16 ? reinterpret_cast<const void*>(k_f_partition<16>)
+                                 : reinterpret_cast<const void*>(k_f_partition<8>);
   HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kFPartThreads, 0));
   return per_cu;
 }
 
-// one block per tile (A/B of the tile shapes at 1.25M / 10M rows: 1024-row tiles 884-886 it/s vs
+// block b takes tiles b, b + grid, ... (A/B of the tile shapes at 1.25M / 10M rows: 1024-row tiles 884-886 it/s vs
 // 855 for two per block, 4096-row tiles at 10M 397.7 vs 394.3 for two 2048-row tiles per block)
 void LaunchFrontierPartition(const FArgs& a, int iters, int grid, hipStream_t s) {
-  if (iters == 4) k_f_partition<4, 1><<<grid, kFPartThreads, 0, s>>>(a);
-  else if (iters == 16) k_f_partition<16, 1><<<grid, kFPartThreads, 0, s>>>(a);
-  else k_f_partition<8, 1><<<grid, kFPartThreads, 0, s>>>(a);
+  if (iters == 4) k_f_partition<4><<<grid, kFPartThreads, 0, s>>>(a);
+  else if (iters == 16) k_f_partition<16><<<grid, kFPartThreads, 0, s>>>(a);
+  else k_f_partition<8><<<grid, kFPartThreads, 0, s>>>(a);
   HIP_CHECK(hipGetLastError());
 }
 
