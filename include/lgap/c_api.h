@@ -340,6 +340,26 @@ LIGHTGBM_C_EXPORT int LGBM_DeviceTestFrontierPartition(DatasetHandle handle, con
                                                        const int32_t* feats, const int32_t* thr, const int32_t* dleft,
                                                        const uint32_t* catbits, int32_t* out_rows, int32_t* out_left,
                                                        int32_t* exp_rows, int32_t* exp_left);
+// The gradient quantizer of a device learner configured by `parameters` (use_quantized_grad),
+// run as training runs it: grad / hess [num_class][num_data] uploaded every round, then quantized
+// class by class, `rounds` times. Outputs per (round, class): out_gh [num_data][2] de-quantized
+// (g, h); out_levels [num_data] g level << 8 | h level, valid when *out_has_levels != 0;
+// out_qmax [2] float bits of max |g|, max |h|; out_true [num_data][2] the inputs kept for
+// quant_train_renew_leaf (untouched otherwise).
+LIGHTGBM_C_EXPORT int LGBM_DeviceTestQuantize(DatasetHandle handle, const char* parameters, int const_hess,
+                                              const float* grad, const float* hess, int num_class, int rounds,
+                                              float* out_gh, uint16_t* out_levels, uint32_t* out_qmax,
+                                              float* out_true, int* out_has_levels);
+// One launch of the linear-leaf Gram kernels over host arrays: raw [num_data][num_feature], leaf
+// l's rows by segs[3 l ..] = (0, start, count) into `rows` or (-1, start, count) for the
+// contiguous rows start .. start + count, its features feats[feat_off[l] .. feat_off[l + 1])
+// (sorted). out [num_leaves][64][64] holds A in rows / columns [0, m) and c in column m
+// (m = features + 1), out_usable [num_leaves] the non-NaN values read before each row's first NaN.
+LIGHTGBM_C_EXPORT int LGBM_DeviceTestLinearGram(const float* raw, int32_t num_data, int32_t num_feature,
+                                                const float* grad, const float* hess, const int32_t* rows,
+                                                int32_t num_rows, const int32_t* segs, int num_leaves,
+                                                const int32_t* feat_off, const int32_t* feats, int chunks,
+                                                double* out, int64_t* out_usable);
 // One device row-sampling pass (the HIP bagging / GOSS kernels) over host arrays: mode 1 bagging,
 // 2 balanced bagging, 3 GOSS; `rounds` > 1 re-bags with the advanced streams and reports the last.
 // grad/hess (num_class * num_rows, class-major) are scaled in place by GOSS. Returns the kept

@@ -99,6 +99,25 @@ void TestFrontierPartition(const Dataset* data, const Config& config, const int*
                            const int* feats, const int* thr, const int* dleft, const uint32_t* catbits, int* out_rows,
                            int* out_left, int* exp_rows, int* exp_left);
 
+// Direct test of the gradient quantizer (tests/test_quantize_kernels.py): a device learner of
+// `config` (Init with const_hess), class-major grad / hess [num_class][N] uploaded afresh every
+// round, then the learner's own QuantizeGradients(class) for every class, `rounds` times (k_qmax
+// and k_quantize with its grid, seed and round counter). Per (round, class): out_gh[N][2] the
+// de-quantized (g, h), out_levels[N] the packed int8 g << 8 | uint8 h levels (written only when
+// the function returns true: integer-level histograms, bins <= 254), out_qmax[2] the bits of
+// max |g| and max |h|, out_true[N][2] the kept inputs (quant_train_renew_leaf only).
+bool TestQuantize(const Dataset* data, const Config& config, bool const_hess, const float* grad, const float* hess,
+                  int num_class, int rounds, float* out_gh, uint16_t* out_levels, uint32_t* out_qmax,
+                  float* out_true);
+// Direct test of the linear-leaf Gram kernels (tests/test_linear_gram_kernel.py), no Dataset:
+// raw[N][F], grad / hess[N]; leaf l reads segs[3 l ..] = (buffer, start, count): buffer 0 the
+// positions [start, start + count) of rows[num_rows], buffer -1 the rows start .. start + count
+// themselves; its features feats[feat_off[l] .. feat_off[l + 1]). One LaunchLinearGram with
+// `chunks` row chunks per leaf -> out[num_leaves][64][64], usable[num_leaves].
+void TestLinearGram(const float* raw, int N, int F, const float* grad, const float* hess, const int* rows,
+                    int num_rows, const int* segs, int num_leaves, const int* feat_off, const int* feats,
+                    int chunks, double* out, long long* usable);
+
 // One pass of the device row-sampling kernels over host arrays (LGBM_DeviceSampleRows):
 // returns the kept-row count, rows in out_rows, GOSS scaling applied to grad / hess.
 int SampleRowsOnDevice(int mode, int num_rows, int num_class, float* grad, float* hess, const float* label,

@@ -14,7 +14,7 @@ import numpy as np
 from ..basic import _LIB, Booster, Dataset, _check
 
 __all__ = ["group_layout", "group_bins", "device_histogram", "device_sample_rows", "booster_gradients",
-           "frontier_histogram", "frontier_partition"]
+           "frontier_histogram", "frontier_partition", "quantize_gradients", "linear_gram"]
 
 
 def group_layout(ds: Dataset) -> Tuple[int, int, int, np.ndarray]:
@@ -178,3 +178,86 @@ def frontier_partition(ds: Dataset, subsets, splits, params: Optional[dict] = No
         bits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), out_rows.ctypes.data_as(i32),
         out_left.ctypes.data_as(i32), exp_rows.ctypes.data_as(i32), exp_left.ctypes.data_as(i32)))
     return out_rows[:rows.size], out_left, exp_rows[:rows.size], exp_left
+
+
+def quantize_gradients(ds: Dataset, grad: np.ndarray, hess: np.ndarray, params: dict, num_class: int = 1,
+                       rounds: int = 1, const_hess: bool = False) -> dict:
+    """The gradient quantizer of a device learner set up by ``params`` (k_qmax, k_quantize), run as
+    training runs it: class-major ``grad`` / ``hess`` uploaded every round and quantized class by
+    class, ``rounds`` times, with the learner's own grid, seed and round counter.
+
+    Returns arrays indexed [round, class]: ``g`` / ``h`` [.., n] float32 the de-quantized values left
+    in place, ``g_level`` / ``h_level`` [.., n] int64 and ``packed`` [.., n] uint16 (None unless the
+    learner keeps integer levels: bins <= 254), ``max_g`` / ``max_h`` float32, and ``true_g`` /
+    ``true_h`` [.., n] float32 (None unless quant_train_renew_leaf)."""
+    ds.construct()
+    n = ds.num_data()
+    g = np.ascontiguousarray(grad, dtype=np.float32).ravel()
+    h = np.ascontiguousarray(hess, dtype=np.float32).ravel()
+    if g.size != num_class * n or h.size != num_class * n:
+        raise ValueError(f"quantize_gradients: {g.size} gradients for {num_class} x {n} rows")
+    p = {"use_quantized_grad": True, **params}
+    gh = np.zeros((rounds, num_class, n, 2), dtype=np.float32)
+    packed = np.zeros((rounds, num_class, n), dtype=np.uint16)
+    qmax = np.zeros((rounds, num_class, 2), dtype=np.uint32)
+    true = np.zeros((rounds, num_class, n, 2), dtype=np.float32)
+    has = ctypes.c_int(0)
+    fp = ctypes.POINTER(ctypes.c_float)
+    _check(_LIB.LGBM_DeviceTestQuantize(
+        ds.handle, ctypes.c_char_p(_param_str(p)), ctypes.c_int(int(const_hess)), g.ctypes.data_as(fp),
+        h.ctypes.data_as(fp), ctypes.c_int(num_class), ctypes.c_int(rounds), gh.ctypes.data_as(fp),
+        packed.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), qmax.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+        true.ctypes.data_as(fp), ctypes.byref(has)))
+    mx = qmax.view(np.float32)
+    renew = str(p.get("quant_train_renew_leaf", False)).lower() in ("true", "1")
+    out = {"g": gh[..., 0], "h": gh[..., 1], "max_g": mx[..., 0], "max_h": mx[..., 1],
+           "packed": None, "g_level": None, "h_level": None,
+           "true_g": true[..., 0] if renew else None, "true_h": true[..., 1] if renew else None}
+    if has.value:
+        out["packed"] = packed
+        out["g_level"] = (packed >> 8).astype(np.uint8).view(np.int8).astype(np.int64)
+        out["h_level"] = (packed & 0xFF).astype(np.int64)
+    return out
+
+
+def linear_gram(raw: np.ndarray, grad: np.ndarray, hess: np.ndarray, leaves, feats, chunks: int = 1
+                ) -> Tuple[np.ndarray, np.ndarray]:
+    """One launch of the linear-leaf Gram kernels (k_linear_gram, k_linear_fold) over host arrays.
+
+    ``raw`` [n, f] float32; ``leaves``: per leaf an array of row numbers, or a ``range`` for the
+    contiguous rows the kernel reads without an index list; ``feats``: per leaf its sorted feature
+    columns. Returns (out [leaves, 64, 64]: A in rows / columns [0, m) and c in column m, with
+    m = features + 1; usable [leaves] int64)."""
+    x = np.ascontiguousarray(raw, dtype=np.float32)
+    n, f = x.shape
+    g = np.ascontiguousarray(grad, dtype=np.float32)
+    h = np.ascontiguousarray(hess, dtype=np.float32)
+    if g.size != n or h.size != n or len(leaves) != len(feats):
+        raise ValueError("linear_gram: inconsistent inputs")
+    nl = len(leaves)
+    segs = np.zeros((nl, 3), dtype=np.int32)
+    lists = []
+    pos = 0
+    for l, rows in enumerate(leaves):
+        if isinstance(rows, range):
+            if rows.step != 1:
+                raise ValueError("linear_gram: contiguous ranges only")
+            segs[l] = (-1, rows.start, len(rows))
+        else:
+            r = np.asarray(rows, dtype=np.int32)
+            segs[l] = (0, pos, r.size)
+            lists.append(r)
+            pos += r.size
+    rows = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0), dtype=np.int32)
+    off = np.zeros(nl + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(c) for c in feats])
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.int32) for c in feats]), dtype=np.int32)
+    out = np.zeros((nl, 64, 64), dtype=np.float64)
+    usable = np.zeros(nl, dtype=np.int64)
+    i32, fp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+    _check(_LIB.LGBM_DeviceTestLinearGram(
+        x.ctypes.data_as(fp), ctypes.c_int32(n), ctypes.c_int32(f), g.ctypes.data_as(fp), h.ctypes.data_as(fp),
+        rows.ctypes.data_as(i32), ctypes.c_int32(rows.size), segs.ctypes.data_as(i32), ctypes.c_int(nl),
+        off.ctypes.data_as(i32), flat.ctypes.data_as(i32), ctypes.c_int(chunks),
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), usable.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+    return out, usable

@@ -1438,6 +1438,32 @@ int LGBM_DeviceTestFrontierPartition(DatasetHandle handle, const char* parameter
   API_END();
 }
 
+// Direct tests of the gradient quantizer and of the linear-leaf Gram kernels (device_api.h
+// TestQuantize / TestLinearGram)
+int LGBM_DeviceTestQuantize(DatasetHandle handle, const char* parameters, int const_hess, const float* grad,
+                            const float* hess, int num_class, int rounds, float* out_gh, uint16_t* out_levels,
+                            uint32_t* out_qmax, float* out_true, int* out_has_levels) {
+  API_BEGIN();
+  Config cfg = ParseConfig(parameters);
+  cfg.device_type = "gpu";
+  *out_has_levels = device::TestQuantize(D(handle)->ds.get(), cfg, const_hess != 0, grad, hess, num_class, rounds,
+                                         out_gh, out_levels, out_qmax, out_true)
+                        ? 1
+                        : 0;
+  API_END();
+}
+
+int LGBM_DeviceTestLinearGram(const float* raw, int32_t num_data, int32_t num_feature, const float* grad,
+                              const float* hess, const int32_t* rows, int32_t num_rows, const int32_t* segs,
+                              int num_leaves, const int32_t* feat_off, const int32_t* feats, int chunks, double* out,
+                              int64_t* out_usable) {
+  API_BEGIN();
+  static_assert(sizeof(long long) == sizeof(int64_t), "usable counts are 64-bit");
+  device::TestLinearGram(raw, num_data, num_feature, grad, hess, rows, num_rows, segs, num_leaves, feat_off, feats,
+                         chunks, out, reinterpret_cast<long long*>(out_usable));
+  API_END();
+}
+
 int LGBM_DeviceSampleRows(int mode, int32_t num_rows, int num_class, float* grad, float* hess, const float* label,
                           double fraction, double pos_fraction, double neg_fraction, double top_rate,
                           double other_rate, int bagging_seed, uint32_t goss_seed, int rounds, int32_t* out_rows,

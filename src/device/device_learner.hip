@@ -2996,6 +2996,39 @@ class DeviceTreeLearner : public TreeLearner {
     }
   }
 
+  // The gradient quantizer as training runs it: per round the class-major (g, h) uploaded again
+  // (a boosting iteration's fresh gradients), then QuantizeGradients(class) for every class in
+  // turn. Per (round, class): out_gh[N] = the de-quantized (g, h) left in gh_, out_levels[N] =
+  // the packed ghq_ levels (QuantHist() only, else untouched), out_qmax[2] = the bits of max |g|,
+  // max |h|, out_true[N] = gh_true_ (quant_train_renew_leaf only). Returns QuantHist().
+  bool TestQuantize(const float* g, const float* h, int num_class, int rounds, float* out_gh, uint16_t* out_levels,
+                    uint32_t* out_qmax, float* out_true) {
+    if (!config_->use_quantized_grad) Log::Fatal("TestQuantize: use_quantized_grad is not set");
+    if (num_class < 1 || rounds < 1) Log::Fatal("TestQuantize: %d classes, %d rounds", num_class, rounds);
+    K_ = num_class;
+    const size_t n = static_cast<size_t>(N_);
+    for (int r = 0; r < rounds; ++r) {
+      DeviceSetGradients(g, h, num_class);
+      for (int c = 0; c < num_class; ++c) {
+        QuantizeGradients(c);
+        const size_t o = (static_cast<size_t>(r) * num_class + c) * n;
+        HIP_CHECK(hipMemcpyAsync(out_gh + 2 * o, gh_.get() + static_cast<size_t>(c) * n, sizeof(float2) * n,
+                                 hipMemcpyDeviceToHost, stream_));
+        if (QuantHist()) {
+          HIP_CHECK(hipMemcpyAsync(out_levels + o, ghq_.get() + static_cast<size_t>(c) * n, sizeof(uint16_t) * n,
+                                   hipMemcpyDeviceToHost, stream_));
+        }
+        HIP_CHECK(hipMemcpyAsync(out_qmax + 2 * (static_cast<size_t>(r) * num_class + c), qmax_.get(), 8,
+                                 hipMemcpyDeviceToHost, stream_));
+        if (config_->quant_train_renew_leaf) {
+          HIP_CHECK(hipMemcpyAsync(out_true + 2 * o, gh_true_.get(), sizeof(float2) * n, hipMemcpyDeviceToHost, stream_));
+        }
+        HIP_CHECK(hipStreamSynchronize(stream_));
+      }
+    }
+    return QuantHist();
+  }
+
   // k_f_partition of k parents at once (row subsets, split by inner feature feats[e] at
   // threshold bin thr[e] / the categorical bins of catbits[e]): out_rows = the device's
   // children lists (lefts in order, then rights), out_left = left counts; exp_rows / exp_left =
@@ -4499,6 +4532,79 @@ void TestFrontierPartition(const Dataset* data, const Config& config, const int*
   DeviceTreeLearner learner(&config, "serial");
   learner.Init(data, false);
   learner.TestFrontierPartition(rows, offsets, k, feats, thr, dleft, catbits, out_rows, out_left, exp_rows, exp_left);
+}
+
+bool TestQuantize(const Dataset* data, const Config& config, bool const_hess, const float* grad, const float* hess,
+                  int num_class, int rounds, float* out_gh, uint16_t* out_levels, uint32_t* out_qmax,
+                  float* out_true) {
+  if (DeviceCount() <= 0) Log::Fatal("TestQuantize: no AMD GPU visible to HIP");
+  DeviceTreeLearner learner(&config, "serial");
+  learner.Init(data, const_hess);
+  return learner.TestQuantize(grad, hess, num_class, rounds, out_gh, out_levels, out_qmax, out_true);
+}
+
+void TestLinearGram(const float* raw, int N, int F, const float* grad, const float* hess, const int* rows,
+                    int num_rows, const int* segs, int num_leaves, const int* feat_off, const int* feats,
+                    int chunks, double* out, long long* usable) {
+  if (DeviceCount() <= 0) Log::Fatal("TestLinearGram: no AMD GPU visible to HIP");
+  if (N < 1 || F < 1 || num_leaves < 1 || chunks < 1 || num_rows < 0) {
+    Log::Fatal("TestLinearGram: %d rows x %d features, %d leaves, %d chunks", N, F, num_leaves, chunks);
+  }
+  // every index the kernel will read, checked here
+  for (int i = 0; i < num_rows; ++i) {
+    if (rows[i] < 0 || rows[i] >= N) Log::Fatal("TestLinearGram: row %d of %d", rows[i], N);
+  }
+  int max_m = 1;
+  std::vector<LeafSeg> hs(num_leaves);
+  if (feat_off[0] != 0) Log::Fatal("TestLinearGram: feat_off[0] = %d", feat_off[0]);
+  for (int l = 0; l < num_leaves; ++l) {
+    const int buf = segs[3 * l], start = segs[3 * l + 1], count = segs[3 * l + 2];
+    const long long end = static_cast<long long>(start) + count;
+    if (buf < -1 || buf > 0 || start < 0 || count < 0 || end > (buf < 0 ? N : num_rows)) {
+      Log::Fatal("TestLinearGram: leaf %d: buffer %d, rows [%d, %lld)", l, buf, start, end);
+    }
+    hs[l].buf = buf;
+    hs[l].start = start;
+    hs[l].count = count;
+    hs[l].pad = 0;
+    const int k = feat_off[l + 1] - feat_off[l];
+    if (k < 0 || k + 1 > kLinMaxM) Log::Fatal("TestLinearGram: leaf %d: %d features (at most %d)", l, k, kLinMaxM - 1);
+    for (int j = feat_off[l]; j < feat_off[l + 1]; ++j) {
+      if (feats[j] < 0 || feats[j] >= F) Log::Fatal("TestLinearGram: feature %d of %d", feats[j], F);
+    }
+    max_m = std::max(max_m, k + 1);
+  }
+  hipStream_t s = 0;
+  std::vector<float2> hgh(N);
+  for (int i = 0; i < N; ++i) hgh[i] = make_float2(grad[i], hess[i]);
+  DevBuf<float> d_raw;
+  DevBuf<float2> d_gh;
+  DevBuf<int> d_rows, d_off, d_feats;
+  DevBuf<LeafSeg> d_segs;
+  DevBuf<double> d_partial(LinearGramPartialDoubles(num_leaves, chunks));
+  DevBuf<double> d_out(static_cast<size_t>(num_leaves) * kLinDim * kLinDim);
+  DevBuf<long long> d_usable(num_leaves);
+  d_raw.Upload(raw, static_cast<size_t>(N) * F, s);
+  d_gh.Upload(hgh, s);
+  const int none = 0;
+  d_rows.Upload(num_rows > 0 ? rows : &none, std::max(1, num_rows), s);
+  d_off.Upload(feat_off, num_leaves + 1, s);
+  d_feats.Upload(feat_off[num_leaves] > 0 ? feats : &none, std::max(1, feat_off[num_leaves]), s);
+  d_segs.Upload(hs, s);
+  LinearGramArgs ga;
+  ga.raw = d_raw.get();
+  ga.F = F;
+  ga.gh = d_gh.get();
+  for (int i = 0; i < kLeafIdxBufs; ++i) ga.idx[i] = i == 0 ? d_rows.get() : nullptr;
+  ga.segs = d_segs.get();
+  ga.feat_off = d_off.get();
+  ga.feats = d_feats.get();
+  ga.num_leaves = num_leaves;
+  ga.chunks = chunks;
+  LaunchLinearGram(ga, max_m, d_partial.get(), d_out.get(), d_usable.get(), s);
+  d_out.Download(out, static_cast<size_t>(num_leaves) * kLinDim * kLinDim, s);
+  d_usable.Download(usable, num_leaves, s);
+  HIP_CHECK(hipStreamSynchronize(s));
 }
 
 void DeviceHistogram(const Dataset* data, const float* grad, const float* hess, const int* rows, int num_rows,

@@ -475,12 +475,13 @@ void GradientQuantizer::Quantize(const score_t* g, const score_t* h, data_size_t
     const double rg = stochastic_ ? rg_[(static_cast<int64_t>(i) + off) % nr] : 0.5;
     const double rh = stochastic_ ? rh_[(static_cast<int64_t>(i) + off) % nr] : 0.5;
     const double x = g[i] * ig;
-    const int qgi = static_cast<int8_t>(g[i] >= 0 ? x + rg : x - rg);  // truncation toward zero
+    // (levels as int: h levels reach bins_, g levels bins_ / 2, beyond int8 from 128 / 256 bins)
+    const int qgi = static_cast<int>(g[i] >= 0 ? x + rg : x - rg);  // truncation toward zero
     qg[i] = static_cast<score_t>(qgi * gscale_);
     if (constant_hessian) {
       qh[i] = static_cast<score_t>(hscale_);
     } else {
-      const int qhi = static_cast<int8_t>(h[i] * ih + rh);
+      const int qhi = static_cast<int>(h[i] * ih + rh);
       qh[i] = static_cast<score_t>(qhi * hscale_);
     }
   }

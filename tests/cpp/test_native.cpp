@@ -532,9 +532,60 @@ void TestScanSkipsChildWithoutHessian() {
   }
 }
 
+// GradientQuantizer::Quantize under deterministic rounding against the levels' definition
+// (tests/quantize_cases.py holds the same formulas for the device kernels): with mg = max |g|,
+// gs = mg / (bins / 2), hs = mh / bins, the level of g is sign(g) * floor(|g * (1 / gs)| + 0.5)
+// and the value returned float(level * gs); h likewise. g levels lie in [-bins / 2, bins / 2] and
+// h levels in [0, bins], so 254 bins need levels wider than int8.
+void TestGradientQuantizerLevels() {
+  const int n = 1001;
+  for (const int bins : {4, 5, 16, 254}) {
+    for (const int pos : {0, n / 2, n - 1}) {
+      lgap::Random rng(bins * 31 + pos);
+      std::vector<float> g(n), h(n), qg(n), qh(n);
+      for (int i = 0; i < n; ++i) {
+        const float p = 0.02f + 0.96f * rng.NextFloat();
+        g[i] = p - (rng.NextFloat() < 0.5f ? 1.f : 0.f);
+        h[i] = p * (1.f - p);
+      }
+      g[pos] = pos == 0 ? -1.5f : 1.5f;  // the maxima, at the row under test
+      h[pos] = 0.3f;
+      lgap::GradientQuantizer q;
+      q.Init(n, bins, 7, false);
+      q.Quantize(g.data(), h.data(), n, false, qg.data(), qh.data());
+      const double mg = static_cast<double>(1.5f), mh = static_cast<double>(0.3f);
+      const double gs = mg / (bins / 2), hs = mh / bins;
+      EXPECT(q.grad_scale() == gs && q.hess_scale() == hs);
+      const int before = g_failures;
+      int lo_g = 0, hi_g = 0, hi_h = 0;
+      for (int i = 0; i < n; ++i) {
+        const double xg = static_cast<double>(g[i]) * (1.0 / gs), xh = static_cast<double>(h[i]) * (1.0 / hs);
+        const int lg = static_cast<int>(std::floor(std::fabs(xg) + 0.5)) * (g[i] < 0.f ? -1 : 1);
+        const int lh = static_cast<int>(std::floor(xh + 0.5));
+        EXPECT(lg >= -(bins / 2) && lg <= bins / 2);
+        EXPECT(lh >= 0 && lh <= bins);
+        EXPECT(qg[i] == static_cast<float>(lg * gs));
+        EXPECT(qh[i] == static_cast<float>(lh * hs));
+        // the host's own levels, recovered from what it returned
+        EXPECT(std::lround(qg[i] / gs) == lg && std::lround(qh[i] / hs) == lh);
+        lo_g = std::min(lo_g, lg);
+        hi_g = std::max(hi_g, lg);
+        hi_h = std::max(hi_h, lh);
+        if (g_failures - before > 8) break;
+      }
+      if (g_failures != before) {
+        std::fprintf(stderr, "  ^ gradient quantizer, %d bins, maxima at row %d\n", bins, pos);
+        continue;
+      }
+      EXPECT((pos == 0 ? lo_g == -(bins / 2) : hi_g == bins / 2) && hi_h == bins);  // the extreme levels occur
+    }
+  }
+}
+
 int main(int argc, char** argv) {
   const std::string data = argc > 1 ? argv[1] : "tests/data";
   TestEnginePlan();
+  TestGradientQuantizerLevels();
   TestRandom();
   TestCommon();
   TestPointwiseMetric();

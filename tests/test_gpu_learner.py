@@ -550,12 +550,13 @@ def test_device_quantized_training(lgb, gpu_required, rng, renew):
     assert (tc["split_feature"], tc["threshold"]) == (tg["split_feature"], tg["threshold"])
 
 
-@pytest.mark.parametrize("bins", [4, 16])
+@pytest.mark.parametrize("bins", [4, 16, 254])
 def test_device_quantized_integer_histograms(lgb, gpu_required, rng, bins, monkeypatch):
     """Quantized training on the frontier engine builds integer-level histograms (int8 g /
     uint8 h per row, packed g32|h32 sums): with deterministic rounding the whole first tree
     matches the host quantized learner, and the model matches the float-histogram path
-    (LGAP_KERNEL=quant_hist=off) in accuracy."""
+    (LGAP_KERNEL=quant_hist=off) in accuracy. 254 bins: the widest levels the packing holds
+    (h levels up to 254, beyond int8 on the host too)."""
     X, z = _policy_data(rng)
     y = (z > 0).astype(float)
     d = {"use_quantized_grad": True, "num_grad_quant_bins": bins, "stochastic_rounding": False}
