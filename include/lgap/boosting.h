@@ -78,6 +78,9 @@ class GBDT {
 
   // returns true when training cannot continue (no split possible)
   virtual bool TrainOneIter(const score_t* gradients, const score_t* hessians);
+  // one iteration from a custom objective's gradients in device memory (fatal unless the
+  // booster is device-resident and has no built-in objective)
+  bool TrainOneIterDevice(const DeviceGradView& view);
   void Train(int snapshot_freq, const std::string& model_output_path);
   virtual void RollbackOneIter();
   bool EvalAndCheckEarlyStopping();
@@ -87,6 +90,9 @@ class GBDT {
   virtual const double* GetTrainingScore(int64_t* out_len);
   int64_t GetNumPredictAt(int data_idx) const;
   void GetPredictAt(int data_idx, double* out, int64_t* out_len);
+  // The raw class-major score of the training set (0) or validation set data_idx - 1 written
+  // into device memory of the caller (out_dev == nullptr: only *out_len and *out_device).
+  void GetRawScoreDevice(int data_idx, int64_t* out_len, int* out_device, double* out_dev);
   void RefitTree(const std::vector<std::vector<int>>& leaf_preds);
   void MergeFrom(const GBDT* other);
   void ShuffleModels(int start_iter, int end_iter);
@@ -146,6 +152,9 @@ class GBDT {
  protected:
   virtual double BoostFromAverage(int class_id, bool update_scorer);
   void Boosting();
+  // where an iteration's gradients came from
+  enum class GradOrigin { kObjective, kHostArrays, kDeviceArrays };
+  bool TrainWithGradients(std::vector<double>* init_scores, GradOrigin source);
   void UpdateScore(const Tree* tree, int cur_tree_id);
   void AddScoreConstant(double v, int cur_tree_id);
   void SyncTrainScoreFromDevice();

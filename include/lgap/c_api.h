@@ -110,6 +110,23 @@ LIGHTGBM_C_EXPORT int LGBM_BoosterUpdateOneIter(BoosterHandle handle, int* is_fi
 LIGHTGBM_C_EXPORT int LGBM_BoosterRefit(BoosterHandle handle, const int32_t* leaf_preds, int32_t nrow, int32_t ncol);
 LIGHTGBM_C_EXPORT int LGBM_BoosterUpdateOneIterCustom(BoosterHandle handle, const float* grad, const float* hess,
                                                       int* is_finished);
+// One iteration from a custom objective's gradients and hessians in the memory of the GPU the
+// booster trains on (anything else is refused). grad_type / hess_type: C_API_DTYPE_FLOAT32 or
+// C_API_DTYPE_FLOAT64; value (row i, class k) of an array is ptr[i * row_stride + k *
+// class_stride], strides in elements. The arrays have been read when the call returns. Fatal
+// for a booster whose score does not live on the device (use LGBM_BoosterUpdateOneIterCustom)
+// and for values that are not finite as float32.
+LIGHTGBM_C_EXPORT int LGBM_BoosterUpdateOneIterCustomDevice(BoosterHandle handle, const void* grad, const void* hess,
+                                                            int grad_type, int hess_type, int32_t nrow,
+                                                            int32_t num_class, int64_t grad_row_stride,
+                                                            int64_t grad_class_stride, int64_t hess_row_stride,
+                                                            int64_t hess_class_stride, int* is_finished);
+// The raw (untransformed) class-major fp64 score of the training set (data_idx 0) or validation
+// set data_idx - 1, written into caller-owned memory of the training GPU; complete on return.
+// out_device_ptr == NULL: only *out_len (values) and *out_device (the GPU's index) are set;
+// otherwise *out_len holds the output's capacity on entry and must equal the score's length.
+LIGHTGBM_C_EXPORT int LGBM_BoosterGetPredictDevice(BoosterHandle handle, int data_idx, int64_t* out_len,
+                                                   int* out_device, double* out_device_ptr);
 LIGHTGBM_C_EXPORT int LGBM_BoosterRollbackOneIter(BoosterHandle handle);
 LIGHTGBM_C_EXPORT int LGBM_BoosterGetCurrentIteration(BoosterHandle handle, int* out_iteration);
 LIGHTGBM_C_EXPORT int LGBM_BoosterNumModelPerIteration(BoosterHandle handle, int* out_tree_per_iteration);

@@ -30,6 +30,19 @@ enum DeviceSamplePlan {
   kSampleBagQuery = 4,   // bagging by query (whole queries kept or dropped)
 };
 
+// Gradients and hessians of one boosting round as two arrays in device memory
+// (Booster.update_device). Value (row i, class k) of an array is ptr[i * row_stride +
+// k * class_stride], strides in elements; each array is fp32 or fp64.
+struct DeviceGradView {
+  const void* grad = nullptr;
+  const void* hess = nullptr;
+  bool grad_f64 = false, hess_f64 = false;
+  int64_t grad_row_stride = 1, grad_class_stride = 0;
+  int64_t hess_row_stride = 1, hess_class_stride = 0;
+  data_size_t nrow = 0;
+  int num_class = 1;
+};
+
 class TreeLearner {
  public:
   virtual ~TreeLearner() = default;
@@ -56,6 +69,15 @@ class TreeLearner {
   virtual void DeviceInitScore(const std::vector<double>& host_score, int num_tree_per_iter) { (void)host_score; (void)num_tree_per_iter; }
   virtual void DeviceComputeGradients(const ObjectiveFunction*) {}
   virtual void DeviceSetGradients(const score_t*, const score_t*, int) {}
+  // gradients / hessians read from arrays in the training device's memory (a custom objective
+  // computed there); returns after the arrays have been read
+  virtual void DeviceSetGradientsFromDevice(const DeviceGradView&);
+  // the device-resident raw score, class-major, of the training set (id < 0) or of device
+  // validation set `id`, copied into device memory of the caller; synchronised before return
+  virtual void DeviceCopyScoreTo(int /*id*/, double* /*out_dev*/, size_t /*len*/);
+  // a host score uploaded into device memory of the caller; synchronised before return
+  virtual void DeviceUploadScoreTo(const double* /*host*/, double* /*out_dev*/, size_t /*len*/);
+  virtual int DeviceId() const { return -1; }
   virtual std::unique_ptr<Tree> DeviceTrain(int class_id, bool is_first_tree) { (void)class_id; (void)is_first_tree; return nullptr; }
   virtual void DeviceAddTreeToScore(const Tree*, int class_id) { (void)class_id; }
   // training metric from the device-resident score of class k (false: evaluate on the host)

@@ -341,6 +341,30 @@ def _is_device_tensor(x: Any) -> bool:
     return _is_torch_tensor(x) and x.is_cuda
 
 
+_DEVICE_MARK = "_lgap_on_device"
+
+
+def device_objective(fn: Callable) -> Callable:
+    """Mark a custom objective as running on the GPU: ``train()`` then drives it through
+    ``Booster.update_device`` (``fn(preds, train_set)`` with ``preds`` a float64 GPU tensor of raw
+    scores, returning ``(grad, hess)`` as GPU tensors). Returns ``fn`` itself, marked."""
+    setattr(fn, _DEVICE_MARK, True)
+    return fn
+
+
+def device_metric(fn: Callable) -> Callable:
+    """Mark a custom metric (``feval``) as running on the GPU: it receives
+    ``Booster.raw_score_device``'s tensor for the training set and every validation set. A device
+    metric always gets **raw** scores, also with a built-in objective (an unmarked ``feval`` gets
+    the objective's transformed output there). Returns ``fn`` itself, marked."""
+    setattr(fn, _DEVICE_MARK, True)
+    return fn
+
+
+def _is_device_callable(fn: Any) -> bool:
+    return bool(getattr(fn, _DEVICE_MARK, False))
+
+
 def _device_tensor_list(data: Any) -> Optional[List[Any]]:
     """``data`` as a list of GPU tensors when it is one GPU tensor or a list of them, else None
     (a torch tensor on the host keeps taking the ``__array__`` path)."""
@@ -1227,6 +1251,102 @@ class Booster:
         self.__inner_predict_buffer.clear()
         return finished.value == 1
 
+    def update_device(self, fobj: Callable, train_set: Optional[Dataset] = None) -> bool:
+        """One boosting iteration from a custom objective that runs on the GPU.
+
+        ``fobj(preds, train_set)`` receives the raw training score as a float64 torch tensor on
+        the training GPU, shaped ``(N,)`` or, for ``K`` trees per iteration, an ``(N, K)`` view of
+        a ``(K, N)`` buffer (the layout ``update`` hands to its objective). ``preds`` is a copy:
+        writing to it does not touch the model. It returns ``(grad, hess)`` as GPU tensors shaped
+        ``(N,)`` / ``(N, K)``, or 1-D of length ``N * K`` in class-major order as in ``update``.
+        float32 and float64 tensors are read in place through their strides (float64 is rounded
+        to float32, to nearest even); other dtypes are converted with ``.to(torch.float32)``.
+
+        Host arrays raise ``TypeError`` and wrong shapes ``ValueError``; a value that is not
+        finite as float32, a booster whose score does not live on the GPU (``device_type=cpu``,
+        DART, random forest, a configuration routed to the host learners) and a built-in
+        objective raise the library's error. Nothing falls back to the host path: use ``update``.
+        Returns True when no further split was possible, like ``update``.
+        """
+        if train_set is not None and train_set is not self.train_set:
+            train_set.construct()
+            _check(_LIB.LGBM_BoosterResetTrainingData(self.handle, train_set.handle))
+            self.train_set = train_set
+            self.__inner_predict_buffer.clear()
+        grad, hess = fobj(self.raw_score_device(0), self.train_set)
+        return self._boost_device(grad, hess)
+
+    def raw_score_device(self, data_idx: int = 0) -> Any:
+        """The raw (untransformed) score of the training set (``data_idx`` 0) or of validation
+        set ``data_idx - 1`` as a float64 torch tensor on the training GPU: ``(N,)``, or an
+        ``(N, K)`` view of a ``(K, N)`` buffer. Each call returns a fresh copy. Raises the
+        library's error for a booster whose scores live on the host (see ``update_device``)."""
+        n = ctypes.c_int64(0)
+        dev = ctypes.c_int(-1)
+        _check(_LIB.LGBM_BoosterGetPredictDevice(self.handle, ctypes.c_int(data_idx), ctypes.byref(n),
+                                                 ctypes.byref(dev), None))
+        import torch
+
+        device = torch.device("cuda", dev.value)
+        with torch.cuda.device(device):
+            out = torch.empty(n.value, dtype=torch.float64, device=device)
+            # the library copies on a stream of its own and returns when the copy is complete
+            torch.cuda.current_stream().synchronize()
+            _check(_LIB.LGBM_BoosterGetPredictDevice(
+                self.handle, ctypes.c_int(data_idx), ctypes.byref(n), ctypes.byref(dev),
+                ctypes.cast(ctypes.c_void_p(out.data_ptr()), ctypes.POINTER(ctypes.c_double))))
+        k = self.num_model_per_iteration()
+        return out.reshape(k, -1).T if k > 1 else out
+
+    def _boost_device(self, grad: Any, hess: Any) -> bool:
+        """``__boost`` for gradients and hessians that are torch tensors on the training GPU."""
+        for name, t in (("gradient", grad), ("Hessian", hess)):
+            if not _is_device_tensor(t):
+                raise TypeError(f"update_device takes the {name} as a torch tensor on the GPU, not "
+                                f"'{type(t).__name__}'"
+                                f"{' on the host' if _is_torch_tensor(t) else ''}; use Booster.update(fobj=...) "
+                                "for host arrays")
+        import torch
+
+        n = self.train_set.num_data() if self.train_set is not None else 0
+        k = self.num_model_per_iteration()
+        if grad.numel() != hess.numel():
+            raise ValueError(f"Lengths of gradient ({grad.numel()}) and Hessian ({hess.numel()}) don't match")
+        if grad.numel() != n * k:
+            raise ValueError(f"Lengths of gradient ({grad.numel()}) and Hessian ({hess.numel()}) don't match "
+                             f"training data length ({n}) * number of models per one iteration ({k})")
+        views = []
+        for name, t in (("gradient", grad), ("Hessian", hess)):
+            if t.layout != torch.strided:
+                raise TypeError(f"update_device takes strided tensors, the {name} is {t.layout}")
+            if t.dtype not in (torch.float32, torch.float64):
+                t = t.to(torch.float32)
+            if t.dim() == 1:
+                # class-major: value (row i, class j) at element j * n + i
+                rs, cs = t.stride(0), n * t.stride(0)
+            elif t.dim() == 2 and tuple(t.shape) == (n, k):
+                rs, cs = t.stride(0), t.stride(1)
+            else:
+                raise ValueError(f"The {name} has shape {tuple(t.shape)}; expected ({n},), ({n * k},) or ({n}, {k})")
+            dtype = C_API_DTYPE_FLOAT32 if t.dtype == torch.float32 else C_API_DTYPE_FLOAT64
+            views.append((t, dtype, rs, cs))
+        (g, g_type, g_rs, g_cs), (h, h_type, h_rs, h_cs) = views
+        finished = ctypes.c_int(0)
+        try:
+            with torch.cuda.device(g.device):
+                # the library reads on a stream of its own: the tensors' producers must be done.
+                # It returns once it has read them, so they may be released afterwards.
+                torch.cuda.current_stream().synchronize()
+                if h.device != g.device:
+                    torch.cuda.current_stream(h.device).synchronize()
+                _check(_LIB.LGBM_BoosterUpdateOneIterCustomDevice(
+                    self.handle, ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(h.data_ptr()), ctypes.c_int(g_type),
+                    ctypes.c_int(h_type), ctypes.c_int32(n), ctypes.c_int32(k), ctypes.c_int64(g_rs),
+                    ctypes.c_int64(g_cs), ctypes.c_int64(h_rs), ctypes.c_int64(h_cs), ctypes.byref(finished)))
+        finally:
+            self.__inner_predict_buffer.clear()
+        return finished.value == 1
+
     def rollback_one_iter(self) -> "Booster":
         _check(_LIB.LGBM_BoosterRollbackOneIter(self.handle))
         self.__inner_predict_buffer.clear()
@@ -1296,8 +1416,14 @@ class Booster:
         if feval is not None:
             data = self.train_set if data_idx == 0 else self.valid_sets[data_idx - 1]
             fevals = feval if isinstance(feval, (list, tuple)) else [feval]
-            preds = self.__inner_predict(data_idx)
+            dev_preds = None  # one raw-score tensor for this set's device metrics
             for fe in fevals:
+                if _is_device_callable(fe):
+                    if dev_preds is None:
+                        dev_preds = self.raw_score_device(data_idx)
+                    preds = dev_preds
+                else:
+                    preds = self.__inner_predict(data_idx)
                 out = fe(preds, data)
                 outs = out if isinstance(out, list) else [out]
                 for name, val, hib in outs:

@@ -13,7 +13,7 @@ from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple, Union
 import numpy as np
 
 from . import callback as cb
-from .basic import Booster, Dataset, LightGBMError, _choose_param_value
+from .basic import Booster, Dataset, LightGBMError, _choose_param_value, _is_device_callable
 
 __all__ = ["train", "cv", "CVBooster"]
 
@@ -65,7 +65,14 @@ def train(params: Dict[str, Any], train_set: Dataset, num_boost_round: int = 100
           feval: Optional[Union[Callable, List[Callable]]] = None, init_model: Optional[Union[str, Booster]] = None,
           feature_name: Any = "auto", categorical_feature: Any = "auto", keep_training_booster: bool = False,
           callbacks: Optional[List[Callable]] = None) -> Booster:
-    """Train a booster for ``num_boost_round`` rounds."""
+    """Train a booster for ``num_boost_round`` rounds.
+
+    A callable objective marked with ``device_objective`` runs through ``Booster.update_device``
+    (GPU tensors in and out), and a ``feval`` marked with ``device_metric`` receives
+    ``Booster.raw_score_device``'s tensor: always raw scores, also with a built-in objective.
+    Unmarked callables get numpy arrays as ever. A marked callable on a booster whose scores
+    live on the host raises the library's error.
+    """
     if not isinstance(train_set, Dataset):
         raise TypeError(f"train() only accepts Dataset object, train_set has type '{type(train_set).__name__}'.")
     if num_boost_round <= 0:
@@ -135,7 +142,12 @@ def train(params: Dict[str, Any], train_set: Dataset, num_boost_round: int = 100
                              end_iteration=init_iteration + num_boost_round, evaluation_result_list=None))
         # like the reference, a finished update (no split possible) does not end the loop:
         # later iterations retry, evaluate and run the callbacks
-        booster.update(fobj=fobj)
+        if fobj is not None and _is_device_callable(fobj):
+            # an objective marked with device_objective: scores and gradients stay on the GPU
+            # (the library refuses a booster that is not device-resident; nothing falls back)
+            booster.update_device(fobj)
+        else:
+            booster.update(fobj=fobj)
         evaluation_result_list = []
         if valid_sets or feval is not None:
             if is_valid_contain_train:

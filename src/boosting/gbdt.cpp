@@ -300,6 +300,31 @@ bool GBDT::TrainOneIter(const score_t* gradients, const score_t* hessians) {
     std::copy(hessians, hessians + hessians_.size(), hessians_.begin());
     if (device_mode_) learner_->DeviceSetGradients(gradients_.data(), hessians_.data(), num_tree_per_iteration_);
   }
+  return TrainWithGradients(&init_scores, custom ? GradOrigin::kHostArrays : GradOrigin::kObjective);
+}
+
+// A custom objective's gradients read from arrays in the training device's memory: they go
+// straight into the learner's buffer, gradients_ / hessians_ are never filled.
+bool GBDT::TrainOneIterDevice(const DeviceGradView& view) {
+  ScopedTimer timer("GBDT::TrainOneIter");
+  if (!device_mode_) {
+    Log::Fatal("update_device needs a booster that keeps its score and gradients on the GPU (device_type=gpu, "
+               "boosting=gbdt, a configuration the device learner serves); use Booster.update(fobj=...) here");
+  }
+  if (objective_ != nullptr) {
+    Log::Fatal("update_device: cannot use custom gradients with a built-in objective (set objective=custom, or call "
+               "Booster.update())");
+  }
+  MaybeInjectFault(iter_);
+  std::vector<double> init_scores(num_tree_per_iteration_, 0.0);
+  learner_->DeviceSetGradientsFromDevice(view);
+  return TrainWithGradients(&init_scores, GradOrigin::kDeviceArrays);
+}
+
+// The rest of an iteration once the gradients are in place (on the device in device mode, in
+// gradients_ / hessians_ otherwise): the row sample, one tree per class, the score update.
+bool GBDT::TrainWithGradients(std::vector<double>* init_scores_ptr, GradOrigin source) {
+  std::vector<double>& init_scores = *init_scores_ptr;
   // bagging / GOSS: drawn on the device from the device-resident gradients when the
   // learner can; otherwise on the host (GOSS then round-trips the gradients)
   int plan = kSampleHost;
@@ -307,8 +332,11 @@ bool GBDT::TrainOneIter(const score_t* gradients, const score_t* hessians) {
   if (plan != kSampleHost) {
     learner_->DeviceSample(plan, iter_);
   } else {
-    const bool need_host_grads = sampler_->is_hessian_change() && device_mode_ && !custom &&
-                                 learner_->SupportsDeviceGradients(objective_);
+    // the host sampler reads gradients that exist only on the device: a built-in objective's
+    // device kernel wrote them, or a custom objective handed them over there
+    const bool on_device_only = source == GradOrigin::kDeviceArrays ||
+                                (source == GradOrigin::kObjective && learner_->SupportsDeviceGradients(objective_));
+    const bool need_host_grads = sampler_->is_hessian_change() && device_mode_ && on_device_only;
     if (need_host_grads) learner_->DeviceGetGradients(&gradients_, &hessians_);
     const bool rebag = sampler_->Bagging(iter_, gradients_.data(), hessians_.data());
     if (rebag) {
@@ -560,6 +588,26 @@ void GBDT::GetPredictAt(int data_idx, double* out, int64_t* out_len) {
   } else {
     std::copy(raw, raw + *out_len, out);
   }
+}
+
+void GBDT::GetRawScoreDevice(int data_idx, int64_t* out_len, int* out_device, double* out_dev) {
+  if (!device_mode_) {
+    Log::Fatal("raw_score_device needs a booster that keeps its scores on the GPU (device_type=gpu, boosting=gbdt, a "
+               "configuration the device learner serves); use Booster.update(fobj=...) / eval, which read host scores");
+  }
+  if (data_idx < 0 || static_cast<size_t>(data_idx) > valid_score_.size()) Log::Fatal("Invalid data index %d", data_idx);
+  const data_size_t n = data_idx == 0 ? num_data_ : valid_data_[data_idx - 1]->num_data();
+  const size_t len = static_cast<size_t>(n) * num_tree_per_iteration_;
+  *out_len = static_cast<int64_t>(len);
+  if (out_device != nullptr) *out_device = learner_->DeviceId();
+  if (out_dev == nullptr) return;
+  if (data_idx == 0) {
+    learner_->DeviceCopyScoreTo(-1, out_dev, len);
+    return;
+  }
+  const size_t d = static_cast<size_t>(data_idx - 1);
+  if (valid_dev_[d] >= 0) learner_->DeviceCopyScoreTo(valid_dev_[d], out_dev, len);
+  else learner_->DeviceUploadScoreTo(ValidScore(d), out_dev, len);  // (a set scored on the host)
 }
 
 void GBDT::Train(int snapshot_freq, const std::string& model_output_path) {

@@ -941,6 +941,47 @@ int LGBM_BoosterUpdateOneIterCustom(BoosterHandle handle, const float* grad, con
   API_END();
 }
 
+int LGBM_BoosterUpdateOneIterCustomDevice(BoosterHandle handle, const void* grad, const void* hess, int grad_type,
+                                          int hess_type, int32_t nrow, int32_t num_class, int64_t grad_row_stride,
+                                          int64_t grad_class_stride, int64_t hess_row_stride, int64_t hess_class_stride,
+                                          int* is_finished) {
+  API_BEGIN();
+  auto f64 = [](int t, const char* what) {
+    if (t != C_API_DTYPE_FLOAT32 && t != C_API_DTYPE_FLOAT64) Log::Fatal("update_device: the %s must be float32 or float64", what);
+    return t == C_API_DTYPE_FLOAT64;
+  };
+  DeviceGradView v;
+  v.grad = grad;
+  v.hess = hess;
+  v.grad_f64 = f64(grad_type, "gradient");
+  v.hess_f64 = f64(hess_type, "hessian");
+  v.grad_row_stride = grad_row_stride;
+  v.grad_class_stride = grad_class_stride;
+  v.hess_row_stride = hess_row_stride;
+  v.hess_class_stride = hess_class_stride;
+  v.nrow = nrow;
+  v.num_class = num_class;
+  std::unique_lock<std::shared_mutex> lk(B(handle)->mu_);
+  *is_finished = B(handle)->boosting_->TrainOneIterDevice(v) ? 1 : 0;
+  API_END();
+}
+
+int LGBM_BoosterGetPredictDevice(BoosterHandle handle, int data_idx, int64_t* out_len, int* out_device,
+                                 double* out_device_ptr) {
+  API_BEGIN();
+  std::unique_lock<std::shared_mutex> lk(B(handle)->mu_);
+  GBDT* g = B(handle)->boosting_.get();
+  int64_t len = 0;
+  g->GetRawScoreDevice(data_idx, &len, out_device, nullptr);
+  if (out_device_ptr != nullptr) {
+    if (*out_len != len) Log::Fatal("raw_score_device: the score holds %lld values, the output %lld",
+                                    static_cast<long long>(len), static_cast<long long>(*out_len));
+    g->GetRawScoreDevice(data_idx, &len, out_device, out_device_ptr);
+  }
+  *out_len = len;
+  API_END();
+}
+
 int LGBM_BoosterRollbackOneIter(BoosterHandle handle) {
   API_BEGIN();
   std::unique_lock<std::shared_mutex> lk(B(handle)->mu_);

@@ -820,6 +820,91 @@ class DeviceTreeLearner : public TreeLearner {
     }
   }
 
+  // `p` is memory of this learner's device (hipMalloc'd by anyone in the process, torch included)
+  void RequireTrainingDeviceMemory(const void* p, const char* who, const char* what) const {
+    hipPointerAttribute_t attr{};
+    const hipError_t e = p != nullptr ? hipPointerGetAttributes(&attr, p) : hipErrorInvalidValue;
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (e != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)) {
+      Log::Fatal("%s: the %s is not GPU memory; use Booster.update(fobj=...) for host arrays", who, what);
+    }
+    if (attr.device != device_id_) {
+      Log::Fatal("%s: the %s lives on GPU %d, this booster trains on GPU %d", who, what, attr.device, device_id_);
+    }
+  }
+
+  // A custom objective's gradients, computed on this device: one pass narrows them to fp32,
+  // interleaves them class-major into gh_ and flags values that are not finite. gh_ keeps its
+  // address (captured tree graphs hold it). The wait at the end is also what lets the caller
+  // release its arrays on return.
+  void DeviceSetGradientsFromDevice(const DeviceGradView& v) override {
+    ScopedTimer timer("Device::SetGradientsFromDevice");
+    const char* who = "update_device";
+    if (v.nrow != N_ || v.num_class != K_) {
+      Log::Fatal("%s: gradients of %d rows x %d classes, the booster trains %d rows x %d trees per iteration", who,
+                 v.nrow, v.num_class, N_, K_);
+    }
+    const size_t n = static_cast<size_t>(K_) * N_;
+    if (n == 0 || gh_.size() < n) Log::Fatal("%s: the device gradient buffer is not initialised", who);
+    if (v.grad_row_stride < 0 || v.grad_class_stride < 0 || v.hess_row_stride < 0 || v.hess_class_stride < 0) {
+      Log::Fatal("%s: negative strides are not supported", who);
+    }
+    GradSource g{v.grad, v.grad_f64, v.grad_row_stride, v.grad_class_stride};
+    GradSource h{v.hess, v.hess_f64, v.hess_row_stride, v.hess_class_stride};
+    auto last = [&](const GradSource& s) {
+      const long long off = (static_cast<long long>(N_) - 1) * s.rs + (static_cast<long long>(K_) - 1) * s.cs;
+      return static_cast<const char*>(s.ptr) + off * (s.f64 ? 8 : 4);
+    };
+    RequireTrainingDeviceMemory(g.ptr, who, "gradient");
+    RequireTrainingDeviceMemory(last(g), who, "gradient");
+    RequireTrainingDeviceMemory(h.ptr, who, "hessian");
+    RequireTrainingDeviceMemory(last(h), who, "hessian");
+    if (grad_flag_.size() < 1) grad_flag_.Resize(1);
+    HIP_CHECK(hipMemsetAsync(grad_flag_.get(), 0, sizeof(unsigned), stream_));
+    LaunchSetGradients(g, h, N_, K_, gh_.get(), grad_flag_.get(), num_cu_, stream_);
+    unsigned* flag = pin_grad_flag_.Get(1);
+    HIP_CHECK(hipMemcpyAsync(flag, grad_flag_.get(), sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    if (*flag != 0) {
+      Log::Fatal("%s: the %s not finite as float32 (NaN, infinity or beyond the float range)", who,
+                 (*flag & kSetGradBadGrad) && (*flag & kSetGradBadHess) ? "gradient and the hessian hold values that are"
+                 : (*flag & kSetGradBadGrad)                            ? "gradient holds a value that is"
+                                                                        : "hessian holds a value that is");
+    }
+  }
+
+  void DeviceCopyScoreTo(int id, double* out_dev, size_t len) override {
+    const char* who = "raw_score_device";
+    const double* src = nullptr;
+    size_t have = 0;
+    if (id < 0) {
+      FlushScore();  // (the frontier's deferred leaf add)
+      src = score_.get();
+      have = static_cast<size_t>(K_) * N_;
+    } else {
+      if (id >= static_cast<int>(valid_.size())) Log::Fatal("%s: no device validation set %d", who, id);
+      src = valid_[id]->score.get();
+      have = valid_[id]->score.size();
+    }
+    if (len != have) Log::Fatal("%s: the score holds %zu values, the output %zu", who, have, len);
+    if (len == 0) return;
+    RequireTrainingDeviceMemory(out_dev, who, "output");
+    RequireTrainingDeviceMemory(out_dev + len - 1, who, "output");
+    HIP_CHECK(hipMemcpyAsync(out_dev, src, len * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+
+  void DeviceUploadScoreTo(const double* host, double* out_dev, size_t len) override {
+    if (len == 0) return;
+    const char* who = "raw_score_device";
+    RequireTrainingDeviceMemory(out_dev, who, "output");
+    RequireTrainingDeviceMemory(out_dev + len - 1, who, "output");
+    HIP_CHECK(hipMemcpyAsync(out_dev, host, len * sizeof(double), hipMemcpyHostToDevice, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+
+  int DeviceId() const override { return device_id_; }
+
   void DeviceGetScore(std::vector<double>* out) const override {
     FlushScore();
     out->resize(static_cast<size_t>(K_) * N_);
@@ -4340,6 +4425,8 @@ class DeviceTreeLearner : public TreeLearner {
   PinnedBuf<LeafRange> pin_range_;
   PinnedBuf<double> pin_lout_;
   PinnedBuf<float2> pin_gh_;
+  DevBuf<unsigned> grad_flag_;       // DeviceSetGradientsFromDevice: non-finite bits of the pass
+  PinnedBuf<unsigned> pin_grad_flag_;
   PinnedBuf<char> pin_tree_;
   PinnedBuf<char> pin_tree_ring_[2];  // TraverseTreeCompact staging (see there)
   DevBuf<char> ttree_buf_;             // its device copy (stream-ordered reuse)

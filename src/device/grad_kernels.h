@@ -81,6 +81,22 @@ void LaunchXendcgGrad(const XendcgArgs& a, hipStream_t s);
 
 void LaunchAddConstant(double* score, int n, double v, hipStream_t s);
 
+// Gradients / hessians given as device arrays (set_grad_kernels.hip): value (row i, class k) of
+// a source is ptr[i * rs + k * cs], strides in elements, fp32 or fp64 (narrowed to nearest even).
+struct GradSource {
+  const void* ptr = nullptr;
+  bool f64 = false;
+  long long rs = 1, cs = 0;
+};
+enum class SetGradPath { kRows, kTile, kGather };
+// which kernel serves the two layouts (a pure function of the strides and the shape)
+SetGradPath PlanSetGradients(const GradSource& g, const GradSource& h, int n, int num_class);
+constexpr unsigned kSetGradBadGrad = 1u, kSetGradBadHess = 2u;  // bits of *flag
+// gh[k * n + i] = (g(i, k), h(i, k)); ORs kSetGradBad* into *flag (device, zeroed by the caller)
+// for values that are not finite as fp32
+void LaunchSetGradients(const GradSource& g, const GradSource& h, int n, int num_class, float2* gh, unsigned* flag,
+                        int num_cu, hipStream_t s);
+
 // sum over rows of the pointwise metric's weighted row loss (PmRowTerm) -> *out (device);
 // `partial` holds max_blocks doubles
 void LaunchPointwiseMetric(const PwMetricParams& p, const double* score, const float* label, const float* weight, int n,

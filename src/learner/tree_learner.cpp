@@ -28,6 +28,18 @@ std::unique_ptr<TreeLearner> CreateHost(const std::string& learner_type, bool li
 
 }  // namespace
 
+// Only a learner that owns the score on the device serves these (the boosting loop refuses
+// earlier, with the advice to use Booster.update; reaching them is a routing bug).
+void TreeLearner::DeviceSetGradientsFromDevice(const DeviceGradView&) {
+  Log::Fatal("This tree learner keeps its gradients on the host: pass host arrays through Booster.update(fobj=...)");
+}
+void TreeLearner::DeviceCopyScoreTo(int, double*, size_t) {
+  Log::Fatal("This tree learner keeps its scores on the host: read them through Booster.update(fobj=...) / eval");
+}
+void TreeLearner::DeviceUploadScoreTo(const double*, double*, size_t) {
+  Log::Fatal("This tree learner keeps its scores on the host: read them through Booster.update(fobj=...) / eval");
+}
+
 std::unique_ptr<TreeLearner> TreeLearner::Create(const std::string& learner_type, const std::string& device_type,
                                                  bool linear_tree, const Config* config, const Dataset* train) {
   if (device_type == "gpu" || device_type == "cuda") {
