@@ -80,8 +80,9 @@ class TreeLearner {
   virtual int DeviceId() const { return -1; }
   virtual std::unique_ptr<Tree> DeviceTrain(int class_id, bool is_first_tree) { (void)class_id; (void)is_first_tree; return nullptr; }
   virtual void DeviceAddTreeToScore(const Tree*, int class_id) { (void)class_id; }
-  // training metric from the device-resident score of class k (false: evaluate on the host)
-  virtual bool DeviceEvalPointwise(const PwMetricParams&, int /*k*/, double* /*sum*/) { return false; }
+  // pointwise metric from the device-resident score of class k of the training set (id < 0) or
+  // of device validation set `id`: the weighted loss sum (false: evaluate on the host)
+  virtual bool DeviceEvalPointwise(int /*id*/, const PwMetricParams&, int /*k*/, double* /*sum*/) { return false; }
   virtual void DeviceAddConstant(double, int class_id) { (void)class_id; }
   virtual void DeviceGetScore(std::vector<double>*) const {}
   virtual void DeviceGetGradients(std::vector<score_t>*, std::vector<score_t>*) const {}
@@ -102,7 +103,6 @@ class TreeLearner {
   virtual void DeviceValidAddConstant(int /*id*/, double, int /*class_id*/) {}
   virtual void DeviceGetValidScore(int /*id*/, std::vector<double>*) {}
   virtual void DeviceSetValidScore(int /*id*/, const std::vector<double>&) {}
-  virtual bool DeviceEvalPointwiseValid(int /*id*/, const PwMetricParams&, int /*k*/, double* /*sum*/) { return false; }
   // Ranking / AUC metric of the training set (id < 0) or device validation set `id`, class k,
   // on the device score: raw sums for Metric::FinishRank (false: evaluate on the host)
   virtual bool DeviceEvalRank(int /*id*/, const RankMetricSpec&, int /*k*/, std::vector<double>* /*out*/) { return false; }

@@ -429,7 +429,7 @@ std::vector<double> GBDT::EvalTraining(const Metric* m, const double** score) {
   if (allow && device_mode_ && num_tree_per_iteration_ == 1 && DeviceMetricsAllowed() &&
       m->DevicePointwise(objective_, &p)) {
     double sum = 0.0;
-    if (learner_->DeviceEvalPointwise(p, 0, &sum)) return m->FinishSum(sum);
+    if (learner_->DeviceEvalPointwise(-1, p, 0, &sum)) return m->FinishSum(sum);
   }
   // ranking / AUC metrics: sorted on the device, only their sums come back
   RankMetricSpec rs;
@@ -462,7 +462,7 @@ std::vector<double> GBDT::EvalValid(size_t d, const Metric* m) {
   PwMetricParams p;
   if (valid_dev_[d] >= 0 && num_tree_per_iteration_ == 1 && m->DevicePointwise(objective_, &p)) {
     double sum = 0.0;
-    if (learner_->DeviceEvalPointwiseValid(valid_dev_[d], p, 0, &sum)) return m->FinishSum(sum);
+    if (learner_->DeviceEvalPointwise(valid_dev_[d], p, 0, &sum)) return m->FinishSum(sum);
   }
   RankMetricSpec rs;
   const char* off = std::getenv("LGAP_DEVICE_METRICS");

@@ -67,7 +67,10 @@
 // Gram systems, linear_kernels.hip).
 //
 // After either engine: leaf outputs / renew (leaf_kernels.hip), then the score
-// update walks the new tree in group-bin space (traverse_kernels.hip).
+// update walks the new tree in group-bin space (traverse_kernels.hip; the tree is packed by
+// traverse_pack.h and staged through runtime_internal.h's StagingRing). Metrics on the
+// device-resident scores are evaluated by metric_eval.{h,hip} over a view of a score
+// (ScoreViewOf below).
 //
 // Reference parity: serial_tree_learner.cpp:170-680 (growth loop, smaller /
 // larger handling, BeforeFindBestSplit), feature_histogram.hpp:830-1057
@@ -90,7 +93,7 @@
 #include "device/grad_kernels.h"
 #include "device/hip_common.h"
 #include "device/leaf_kernels.h"
-#include "device/metric_kernels.h"
+#include "device/metric_eval.h"
 #include "device/linear_kernels.h"
 #include "device/runtime_internal.h"
 #include "device/frontier.h"
@@ -158,26 +161,6 @@ const char* KernelOverride(const char* key) {
 
 using namespace seq;  // NOLINT: the sequential chain's kernels and argument block
 
-template <typename T>
-class PinnedBuf {
- public:
-  ~PinnedBuf() {
-    if (p_) (void)hipHostFree(p_);
-  }
-  T* Get(size_t n) {
-    if (n > n_) {
-      if (p_) HIP_CHECK(hipHostFree(p_));
-      HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&p_), std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault));
-      n_ = n;
-    }
-    return p_;
-  }
-
- private:
-  T* p_ = nullptr;
-  size_t n_ = 0;
-};
-
 class DeviceTreeLearner : public TreeLearner {
  public:
   // routed: made by TreeLearner::Create, whose engine plan sent the configuration here (the
@@ -187,9 +170,6 @@ class DeviceTreeLearner : public TreeLearner {
 
   ~DeviceTreeLearner() override {
     if (fres_host_) (void)hipHostFree(fres_host_);
-    for (auto& ev : tree_evt_) {
-      if (ev) (void)hipEventDestroy(ev);
-    }
     if (graph_exec_) (void)hipGraphExecDestroy(graph_exec_);
     for (auto& kv : fgraphs_) (void)hipGraphExecDestroy(kv.second);
     if (fcont_) (void)hipGraphExecDestroy(fcont_);
@@ -297,8 +277,6 @@ class DeviceTreeLearner : public TreeLearner {
     cand_stride_ = static_cast<int>(kb + ib);
     if (plan_.voting) SetupVoting();
   }
-
-  static size_t Round256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
   // Voting: top-k width, the packed elected-histogram row, and the global candidate table
   // (one row of 2 x top_k positions). The xGMI exchange buffer reuses the histogram receive
@@ -875,22 +853,13 @@ class DeviceTreeLearner : public TreeLearner {
 
   void DeviceCopyScoreTo(int id, double* out_dev, size_t len) override {
     const char* who = "raw_score_device";
-    const double* src = nullptr;
-    size_t have = 0;
-    if (id < 0) {
-      FlushScore();  // (the frontier's deferred leaf add)
-      src = score_.get();
-      have = static_cast<size_t>(K_) * N_;
-    } else {
-      if (id >= static_cast<int>(valid_.size())) Log::Fatal("%s: no device validation set %d", who, id);
-      src = valid_[id]->score.get();
-      have = valid_[id]->score.size();
-    }
-    if (len != have) Log::Fatal("%s: the score holds %zu values, the output %zu", who, have, len);
+    ScoreView v;
+    if (!ScoreViewOf(id, &v)) Log::Fatal("%s: no device validation set %d", who, id);
+    if (len != v.len) Log::Fatal("%s: the score holds %zu values, the output %zu", who, v.len, len);
     if (len == 0) return;
     RequireTrainingDeviceMemory(out_dev, who, "output");
     RequireTrainingDeviceMemory(out_dev + len - 1, who, "output");
-    HIP_CHECK(hipMemcpyAsync(out_dev, src, len * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(out_dev, v.score, len * sizeof(double), hipMemcpyDeviceToDevice, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
   }
 
@@ -917,19 +886,44 @@ class DeviceTreeLearner : public TreeLearner {
     LaunchAddConstant(score_.get() + static_cast<size_t>(k) * N_, N_, v, stream_);
   }
 
-  bool DeviceEvalPointwise(const PwMetricParams& p, int k, double* sum) override {
-    if (score_.size() < static_cast<size_t>(k + 1) * N_ || N_ <= 0) return false;
-    ScopedTimer timer("Device::EvalMetric");
-    FlushScore();
-    EnsureMetricLabels();
-    LaunchPointwiseMetric(p, score_.get() + static_cast<size_t>(k) * N_, metric_label_.get(),
-                          metric_weight_.size() ? metric_weight_.get() : nullptr, N_, metric_partial_.get(),
-                          kMetricBlocks, metric_partial_.get() + kMetricBlocks, stream_);
-    double* h = pin_lout_.Get(1);
-    HIP_CHECK(hipMemcpyAsync(h, metric_partial_.get() + kMetricBlocks, sizeof(double), hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    *sum = h[0];
+  // The score of the training set (id < 0: the deferred leaf add applied, the raw labels and
+  // weights uploaded at first use) or of device validation set `id`; false: no such set. A set
+  // without labels has label == nullptr (MetricEval holds no metric for it).
+  bool ScoreViewOf(int id, ScoreView* v) {
+    if (id < 0) {
+      FlushScore();
+      const Metadata& md = data_->metadata();
+      if (metric_label_.size() == 0 && md.label() != nullptr) {
+        metric_label_.Upload(md.label(), N_, stream_);  // the raw labels (objectives may relabel theirs)
+        if (md.weights()) metric_weight_.Upload(md.weights(), N_, stream_);
+      }
+      // (an empty DevBuf's pointer is nullptr; the score holds K_ x N_ values once DeviceInitScore ran)
+      *v = {score_.get(), score_.size(), metric_label_.get(), metric_weight_.get(), md.label(), N_};
+      return true;
+    }
+    if (id >= static_cast<int>(valid_.size())) return false;
+    const DevValid& d = *valid_[id];
+    *v = {d.score.get(), d.score.size(), d.label.get(), d.weight.get(), d.host_label, d.n};
     return true;
+  }
+
+  // ---- metrics on the device score (metric_eval.h) of the training set (id < 0) or a device
+  // validation set
+  bool DeviceEvalPointwise(int id, const PwMetricParams& p, int k, double* sum) override {
+    ScoreView v;
+    return ScoreViewOf(id, &v) && metrics_.Pointwise(v, p, k, id < 0 ? "Device::EvalMetric" : "Device::EvalValid", sum, stream_);
+  }
+  bool DeviceEvalMulti(int id, const MultiMetricParams& p, double* sum) override {
+    ScoreView v;
+    return ScoreViewOf(id, &v) && metrics_.Multi(v, p, sum, stream_);
+  }
+  bool DeviceEvalAucMu(int id, const AucMuSpec& spec, std::vector<double>* out) override {
+    ScoreView v;
+    return ScoreViewOf(id, &v) && metrics_.AucMu(v, spec, out, stream_);
+  }
+  bool DeviceEvalRank(int id, const RankMetricSpec& spec, int k, std::vector<double>* out) override {
+    ScoreView v;
+    return ScoreViewOf(id, &v) && metrics_.Rank(v, spec, k, out, stream_);
   }
 
   void DeviceAddTreeToScore(const Tree* tree, int k) override {
@@ -973,10 +967,7 @@ class DeviceTreeLearner : public TreeLearner {
     const size_t map_part = Round256(seg_bytes + off_bytes + sizeof(double) * nseg);
     const CompactLayout z = bag ? CompactTreeLayout(tree) : CompactLayout{0, 0, 0, 0};
     const size_t bytes = map_part + z.total;
-    const int slot = tree_slot_++ & 1;
-    if (tree_evt_[slot] == nullptr) HIP_CHECK(hipEventCreateWithFlags(&tree_evt_[slot], hipEventDisableTiming));
-    else HIP_CHECK(hipEventSynchronize(tree_evt_[slot]));
-    char* hp = pin_tree_ring_[slot].Get(bytes);
+    char* hp = tree_ring_.Begin(bytes);
     LeafSeg* segs = reinterpret_cast<LeafSeg*>(hp);
     int* off = reinterpret_cast<int*>(hp + seg_bytes);
     double* lv = reinterpret_cast<double*>(hp + seg_bytes + off_bytes);
@@ -1010,14 +1001,9 @@ class DeviceTreeLearner : public TreeLearner {
       segs[nl].pad = 0;  // (ascending)
       off[nl + 1] = N_;
       lv[nl] = 0.0;
-      PackCompactTree(tree, hp + map_part, z);
+      PackCompactTree(tree, data_, hp + map_part, z);
     }
-    if (ttree_buf_.size() < bytes) {
-      HIP_CHECK(hipStreamSynchronize(stream_));  // queued score updates still read the old buffer
-      ttree_buf_.Resize(bytes);
-    }
-    HIP_CHECK(hipMemcpyAsync(ttree_buf_.get(), hp, bytes, hipMemcpyHostToDevice, stream_));
-    HIP_CHECK(hipEventRecord(tree_evt_[slot], stream_));
+    const char* db = tree_ring_.Commit(stream_);
     const size_t bound_ints = LeafTileBoundsInts(N_, nseg);
     const size_t map_bytes = Round256(static_cast<size_t>(N_) * (nseg > 256 ? 2 : 1));
     if (leaf_bounds_.size() < bound_ints || leaf_map_.size() < map_bytes || pend_lv_.size() < static_cast<size_t>(kLMMaxLeaves)) {
@@ -1030,7 +1016,6 @@ class DeviceTreeLearner : public TreeLearner {
     for (int i = 0; i < kLeafIdxBufs; ++i) la.idx[i] = i < kFrontierIdx ? idx_[i].get() : nullptr;
     static_assert(kFrontierIdx <= kLeafOobBuf, "the out-of-bag list's index-buffer id");
     la.idx[kLeafOobBuf] = bag ? oob_.get() : nullptr;
-    const char* db = ttree_buf_.get();
     la.segs = reinterpret_cast<const LeafSeg*>(db);
     la.seg_off = reinterpret_cast<const int*>(db + seg_bytes);
     la.leaf_value = reinterpret_cast<const double*>(db + seg_bytes + off_bytes);
@@ -1038,13 +1023,10 @@ class DeviceTreeLearner : public TreeLearner {
     la.n = N_;
     LaunchLeafMap(la, leaf_bounds_.get(), leaf_map_.get(), pend_lv_.get(), stream_);
     if (bag) {
-      const char* dt = db + map_part;
       const bool cols = stride_dw_ > 16 && colbins_.size() >= static_cast<size_t>(G_) * N_ * width_;
       LaunchLeafMapList(cols ? colbins_.get() : nullptr, rowbins_.get(), stride_dw_, width_, N_, oob_.get(),
-                        N_ - bag_cnt_, reinterpret_cast<const TNode*>(dt), nl - 1,
-                        reinterpret_cast<const TCat*>(dt + z.cat), reinterpret_cast<const uint32_t*>(dt + z.bit), nseg,
-                        leaf_map_.get(), KernelOverride("oob_rows") ? std::atoi(KernelOverride("oob_rows")) : 4,
-                        num_cu_, stream_);
+                        N_ - bag_cnt_, CompactTreeAt(db + map_part, z, nl), nseg, leaf_map_.get(),
+                        KernelOverride("oob_rows") ? std::atoi(KernelOverride("oob_rows")) : 4, num_cu_, stream_);
     }
     pend_.on = true;
     pend_.k = k;
@@ -1122,116 +1104,21 @@ class DeviceTreeLearner : public TreeLearner {
     HIP_CHECK(hipStreamSynchronize(stream_));
   }
 
-  // Compact tree staging (traverse_kernels.h TNode / TCat): offsets of the nodes, the
-  // categorical node data, the leaf values and the categorical words in one upload
-  struct CompactLayout {
-    size_t cat, leaf, bit, total;
-  };
-  static CompactLayout CompactTreeLayout(const Tree* tree) {
-    const int nn = tree->num_leaves() - 1, nl = tree->num_leaves();
-    const size_t node_bytes = Round256(sizeof(TNode) * nn), cat_bytes = Round256(sizeof(TCat) * nn);
-    const size_t leaf_bytes = Round256(sizeof(double) * nl);
-    const size_t bit_bytes = sizeof(uint32_t) * std::max<size_t>(1, tree->cat_threshold_inner().size());
-    CompactLayout z;
-    z.cat = node_bytes;
-    z.leaf = z.cat + cat_bytes;
-    z.bit = z.leaf + leaf_bytes;
-    z.total = z.bit + bit_bytes;
-    return z;
-  }
-  void PackCompactTree(const Tree* tree, char* hp, const CompactLayout& z) const {
-    const int nn = tree->num_leaves() - 1, nl = tree->num_leaves();
-    const auto& cb = tree->cat_boundaries_inner();
-    const auto& ct = tree->cat_threshold_inner();
-    TNode* nodes = reinterpret_cast<TNode*>(hp);
-    TCat* cats = reinterpret_cast<TCat*>(hp + z.cat);
-    for (int i = 0; i < nn; ++i) {
-      const FeatureInfo& fi = data_->feature(tree->split_feature_inner(i));
-      const int8_t dt = tree->decision_type(i);
-      const int missing = Tree::GetMissingType(dt);
-      const bool dleft = Tree::GetDecisionType(dt, kDefaultLeftMask);
-      const int offset = fi.offset, nb = fi.num_bin, mfb = static_cast<int>(fi.mfb);
-      TNode& d = nodes[i];
-      std::memset(&d, 0, sizeof(d));
-      d.group = static_cast<uint16_t>(fi.group);
-      d.left = static_cast<int16_t>(tree->left_child(i));
-      d.right = static_cast<int16_t>(tree->right_child(i));
-      d.gmiss = -1;
-      if (Tree::GetDecisionType(dt, kCategoricalMask)) {
-        const int ci = static_cast<int>(tree->threshold_in_bin(i));
-        d.flags = kTCat;
-        TCat& c = cats[i];
-        c.offset = offset;
-        c.num_bin = nb;
-        c.mfb = mfb;
-        c.begin = cb[ci];
-        c.nwords = cb[ci + 1] - cb[ci];
-        c.pad = 0;
-        continue;
-      }
-      const int thr = static_cast<int>(tree->threshold_in_bin(i));
-      const int bmiss = missing == 1 ? static_cast<int>(fi.default_bin) : (missing == 2 ? nb - 1 : -1);
-      // stored feature bins k = 0 .. nb - 2 sit at group bins offset + k (the mfb is implicit)
-      d.lo = static_cast<uint16_t>(offset);
-      d.hi = static_cast<uint16_t>(offset + nb - 2);
-      const bool out_left = bmiss == mfb ? dleft : (mfb <= thr);
-      if (bmiss >= 0 && bmiss != mfb) d.gmiss = static_cast<int16_t>(offset + (bmiss < mfb ? bmiss : bmiss - 1));
-      // last group bin whose feature bin is <= thr; below `offset` (thr == mfb == 0) no stored bin
-      // goes left, and tg = 0 makes `gb <= tg` false for every in-range bin (offset >= 1)
-      const int tg = offset + (thr < mfb ? thr : thr - 1);
-      d.tg = static_cast<uint16_t>(tg < offset ? 0 : tg);
-      d.flags = static_cast<uint8_t>((out_left ? kTOutLeft : 0) | (dleft ? kTDefaultLeft : 0));
-    }
-    double* lv = reinterpret_cast<double*>(hp + z.leaf);
-    for (int l = 0; l < nl; ++l) lv[l] = tree->LeafOutput(l);
-    uint32_t* cw = reinterpret_cast<uint32_t*>(hp + z.bit);
-    for (size_t i = 0; i < ct.size(); ++i) cw[i] = ct[i];
-  }
-
-  // Compact traversal (traverse_kernels.h): node predicates precomputed in group-bin space.
-  void TraverseTreeCompact(const Tree* tree, const uint32_t* rowbins, int n, double* s) {
-    const int nn = tree->num_leaves() - 1, nl = tree->num_leaves();
+  // Compact traversal (traverse_kernels.h): node predicates precomputed in group-bin space
+  // (traverse_pack.h), staged through the ring. lin: the leaves' linear models, else nullptr.
+  void TraverseTreeCompact(const Tree* tree, const uint32_t* rowbins, int n, double* s, const LinearLeaves* lin = nullptr) {
     const CompactLayout z = CompactTreeLayout(tree);
-    const size_t node_bytes = z.cat, cat_bytes = z.leaf - z.cat, leaf_bytes = z.bit - z.leaf, total = z.total;
-    // staging ring: the host fills one pinned buffer while the copy out of the other may still
-    // be queued, so the score update returns without waiting for the GPU (the next iteration's
-    // launches queue behind the traversal instead of after a host round trip)
-    const int slot = tree_slot_++ & 1;
-    if (tree_evt_[slot] == nullptr) HIP_CHECK(hipEventCreateWithFlags(&tree_evt_[slot], hipEventDisableTiming));
-    else HIP_CHECK(hipEventSynchronize(tree_evt_[slot]));
-    char* hp = pin_tree_ring_[slot].Get(total);
-    PackCompactTree(tree, hp, z);
-    if (ttree_buf_.size() < total) {
-      HIP_CHECK(hipStreamSynchronize(stream_));  // queued traversals still read the old buffer
-      ttree_buf_.Resize(total);
+    PackCompactTree(tree, data_, tree_ring_.Begin(z.total), z);
+    const CompactTreeDev t = CompactTreeAt(tree_ring_.Commit(stream_), z, tree->num_leaves());
+    if (lin != nullptr) {
+      LaunchTraverseLinear(rowbins, StrideOf(rowbins), width_, n, t, *lin, s, num_cu_, stream_);
+    } else if (rowbins == rowbins_.get() && n == N_ && stride_dw_ > 16 && colbins_.size() >= static_cast<size_t>(G_) * N_ * width_) {
+      LaunchTraverseCols(colbins_.get(), width_, n, t, s, num_cu_, stream_);
+    } else if (nib_ && rowbins == rowbins_.get() && n == N_) {
+      LaunchTraverse(rowbins4_.get(), stride4_dw_, 0, n, t, s, num_cu_, stream_);
+    } else {
+      LaunchTraverse(rowbins, StrideOf(rowbins), width_, n, t, s, num_cu_, stream_);
     }
-    HIP_CHECK(hipMemcpyAsync(ttree_buf_.get(), hp, total, hipMemcpyHostToDevice, stream_));
-    HIP_CHECK(hipEventRecord(tree_evt_[slot], stream_));
-    const char* db = ttree_buf_.get();
-    if (lin_pending_ != nullptr) {
-      LaunchTraverseLinear(rowbins, StrideOf(rowbins), width_, n, reinterpret_cast<const TNode*>(db), nn,
-                           reinterpret_cast<const TCat*>(db + node_bytes),
-                           reinterpret_cast<const uint32_t*>(db + node_bytes + cat_bytes + leaf_bytes),
-                           reinterpret_cast<const double*>(db + node_bytes + cat_bytes), nl, *lin_pending_, s, num_cu_,
-                           stream_);
-      return;
-    }
-    if (rowbins == rowbins_.get() && n == N_ && stride_dw_ > 16 && colbins_.size() >= static_cast<size_t>(G_) * N_ * width_) {
-      LaunchTraverseCols(colbins_.get(), width_, n, reinterpret_cast<const TNode*>(db), nn,
-                         reinterpret_cast<const TCat*>(db + node_bytes),
-                         reinterpret_cast<const uint32_t*>(db + node_bytes + cat_bytes + leaf_bytes),
-                         reinterpret_cast<const double*>(db + node_bytes + cat_bytes), nl, s, num_cu_, stream_);
-      return;
-    }
-    if (nib_ && rowbins == rowbins_.get() && n == N_) {
-      LaunchTraverse(rowbins4_.get(), stride4_dw_, 0, n, reinterpret_cast<const TNode*>(db), nn,
-                     reinterpret_cast<const TCat*>(db + node_bytes), reinterpret_cast<const uint32_t*>(db + node_bytes + cat_bytes + leaf_bytes),
-                     reinterpret_cast<const double*>(db + node_bytes + cat_bytes), nl, s, num_cu_, stream_);
-      return;
-    }
-    LaunchTraverse(rowbins, StrideOf(rowbins), width_, n, reinterpret_cast<const TNode*>(db), nn,
-                   reinterpret_cast<const TCat*>(db + node_bytes), reinterpret_cast<const uint32_t*>(db + node_bytes + cat_bytes + leaf_bytes),
-                   reinterpret_cast<const double*>(db + node_bytes + cat_bytes), nl, s, num_cu_, stream_);
   }
 
   // ---- validation sets on the device: packed rows (training layout), score, labels / weights
@@ -1273,240 +1160,6 @@ class DeviceTreeLearner : public TreeLearner {
     valid_[id]->score.Upload(in, stream_);
     HIP_CHECK(hipStreamSynchronize(stream_));
   }
-  bool DeviceEvalPointwiseValid(int id, const PwMetricParams& p, int k, double* sum) override {
-    DevValid& v = *valid_[id];
-    if (v.label.size() == 0) return false;
-    ScopedTimer timer("Device::EvalValid");
-    if (metric_partial_.size() < static_cast<size_t>(kMetricBlocks + 1)) metric_partial_.Resize(kMetricBlocks + 1);
-    LaunchPointwiseMetric(p, v.score.get() + static_cast<size_t>(k) * v.n, v.label.get(),
-                          v.weight.size() ? v.weight.get() : nullptr, v.n, metric_partial_.get(), kMetricBlocks,
-                          metric_partial_.get() + kMetricBlocks, stream_);
-    double* h = pin_lout_.Get(1);
-    HIP_CHECK(hipMemcpyAsync(h, metric_partial_.get() + kMetricBlocks, sizeof(double), hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    *sum = h[0];
-    return true;
-  }
-
-  bool DeviceEvalMulti(int id, const MultiMetricParams& p, double* sum) override {
-    const double* score = nullptr;
-    const float* label = nullptr;
-    const float* weight = nullptr;
-    int n = 0;
-    if (id < 0) {
-      FlushScore();
-      n = N_;
-      if (n <= 0 || score_.size() < static_cast<size_t>(p.num_class) * N_) return false;
-      EnsureMetricLabels();
-      score = score_.get();
-      label = metric_label_.get();
-      weight = metric_weight_.size() ? metric_weight_.get() : nullptr;
-    } else {
-      if (id >= static_cast<int>(valid_.size())) return false;
-      DevValid& v = *valid_[id];
-      n = v.n;
-      if (v.label.size() == 0 || n <= 0 || v.score.size() < static_cast<size_t>(p.num_class) * n) return false;
-      score = v.score.get();
-      label = v.label.get();
-      weight = v.weight.size() ? v.weight.get() : nullptr;
-    }
-    ScopedTimer timer("Device::EvalMultiMetric");
-    if (metric_partial_.size() < static_cast<size_t>(kMetricBlocks + 1)) metric_partial_.Resize(kMetricBlocks + 1);
-    LaunchMultiMetric(p, score, label, weight, n, metric_partial_.get(), kMetricBlocks, metric_partial_.get() + kMetricBlocks,
-                      stream_);
-    double* h = pin_lout_.Get(1);
-    HIP_CHECK(hipMemcpyAsync(h, metric_partial_.get() + kMetricBlocks, sizeof(double), hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    *sum = h[0];
-    return true;
-  }
-
-  bool DeviceEvalAucMu(int id, const AucMuSpec& spec, std::vector<double>* out) override {
-    const int K = spec.num_class;
-    if (K < 2 || K > kAucMuMaxClass || spec.sorted == nullptr || spec.sizes == nullptr || spec.cw == nullptr) return false;
-    const double* score = nullptr;
-    const float* weight = nullptr;
-    const void* host_label = nullptr;
-    int n = 0;
-    if (id < 0) {
-      FlushScore();
-      n = N_;
-      if (n <= 0 || score_.size() < static_cast<size_t>(K) * N_) return false;
-      EnsureMetricLabels();
-      score = score_.get();
-      weight = metric_weight_.size() ? metric_weight_.get() : nullptr;
-      host_label = data_->metadata().label();
-    } else {
-      if (id >= static_cast<int>(valid_.size())) return false;
-      DevValid& v = *valid_[id];
-      n = v.n;
-      if (v.label.size() == 0 || n <= 0 || v.score.size() < static_cast<size_t>(K) * n) return false;
-      score = v.score.get();
-      weight = v.weight.size() ? v.weight.get() : nullptr;
-      host_label = v.host_label;
-    }
-    if (spec.num_data != n || spec.label != host_label || (spec.weights != nullptr) != (weight != nullptr)) return false;
-    if (static_cast<int>(spec.sorted->size()) != n || static_cast<int>(spec.sizes->size()) != K) return false;
-    ScopedTimer timer("Device::EvalAucMu");
-    auto& slot = aucmu_states_[spec.owner];
-    const int npairs = K * (K - 1) / 2;
-    int maxpair = 0;
-    for (int i = 0; i < K; ++i)
-      for (int j = i + 1; j < K; ++j) maxpair = std::max(maxpair, (*spec.sizes)[i] + (*spec.sizes)[j]);
-    if (!slot || slot->n != n || slot->host_label != host_label) {
-      slot = std::make_unique<AucMuState>();
-      slot->n = n;
-      slot->host_label = host_label;
-      std::vector<int> idx(spec.sorted->begin(), spec.sorted->end());
-      slot->idx.Upload(idx, stream_);
-      HIP_CHECK(hipStreamSynchronize(stream_));  // (idx is a local staging vector)
-      slot->dist.Resize(std::max(maxpair, 1));
-      slot->lab.Resize(std::max(maxpair, 1));
-      slot->w.Resize(std::max(maxpair, 1));
-      slot->scratch.Resize(AucScratchBytes(std::max(maxpair, 1)));
-      slot->out.Resize(2 * static_cast<size_t>(npairs));
-    }
-    AucMuState& st = *slot;
-    AucMuPairArgs pa;
-    pa.score = score;
-    pa.n = n;
-    pa.K = K;
-    pa.idx = st.idx.get();
-    pa.weight = weight;
-    pa.out_score = st.dist.get();
-    pa.out_label = st.lab.get();
-    pa.out_w = st.w.get();
-    const auto& cw = *spec.cw;
-    int istart = 0, q = 0;
-    for (int i = 0; i < K; ++i) {
-      int jstart = istart + (*spec.sizes)[i];
-      for (int j = i + 1; j < K; ++j, ++q) {
-        for (int c = 0; c < K; ++c) pa.v[c] = cw[i][c] - cw[j][c];
-        pa.t1 = pa.v[i] - pa.v[j];
-        pa.istart = istart;
-        pa.ni = (*spec.sizes)[i];
-        pa.jstart = jstart;
-        pa.nj = (*spec.sizes)[j];
-        LaunchAucMuPair(pa, stream_);
-        LaunchAucMetric(false, st.dist.get(), st.lab.get(), weight != nullptr ? st.w.get() : nullptr, pa.ni + pa.nj,
-                        st.scratch.get(), st.scratch.size(), st.out.get() + 2 * q, stream_);
-        jstart += (*spec.sizes)[j];
-      }
-      istart += (*spec.sizes)[i];
-    }
-    std::vector<double> h(2 * static_cast<size_t>(npairs));
-    st.out.Download(h.data(), h.size(), stream_);
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    out->assign(npairs, 0.0);
-    for (int p = 0; p < npairs; ++p) (*out)[p] = h[2 * p];
-    return true;
-  }
-
-  // Ranking / AUC metrics on the device score (metric_kernels.h): the training set (id < 0)
-  // or a device validation set. The metric's per-query tables are uploaded once per metric;
-  // only the metric's raw sums come back (no score download).
-  bool DeviceEvalRank(int id, const RankMetricSpec& spec, int k, std::vector<double>* out) override {
-    const double* score = nullptr;
-    const float* label = nullptr;
-    const float* weight = nullptr;
-    const void* host_label = nullptr;
-    int n = 0;
-    if (id < 0) {
-      FlushScore();
-      n = N_;
-      if (n <= 0 || score_.size() < static_cast<size_t>(k + 1) * N_) return false;
-      EnsureMetricLabels();
-      score = score_.get() + static_cast<size_t>(k) * N_;
-      label = metric_label_.get();
-      weight = metric_weight_.size() ? metric_weight_.get() : nullptr;
-      host_label = data_->metadata().label();
-    } else {
-      if (id >= static_cast<int>(valid_.size())) return false;
-      DevValid& v = *valid_[id];
-      if (v.label.size() == 0) return false;
-      n = v.n;
-      score = v.score.get() + static_cast<size_t>(k) * n;
-      label = v.label.get();
-      weight = v.weight.size() ? v.weight.get() : nullptr;
-      host_label = v.host_label;
-    }
-    if (spec.num_data != n || spec.label != host_label) return false;
-    if ((spec.weights != nullptr) != (weight != nullptr)) return false;
-    const bool query = spec.kind >= RankMetricSpec::kNDCG;
-    if (query && (spec.num_queries <= 0 || spec.query_boundaries == nullptr || spec.eval_at.empty() ||
-                  spec.eval_at.size() > static_cast<size_t>(RankMetricSpec::kMaxEvalAt))) {
-      return false;
-    }
-    ScopedTimer timer("Device::EvalRankMetric");
-    auto& slot = rank_states_[spec.owner];
-    if (!slot || slot->kind != spec.kind || slot->n != n || slot->nq != spec.num_queries || slot->host_label != host_label ||
-        slot->host_qb != static_cast<const void*>(spec.query_boundaries) || slot->ks != spec.eval_at) {
-      // built aside and installed only when complete: a rejected spec leaves no half-built
-      // state behind a matching key
-      auto fresh = std::make_unique<RankEvalState>();
-      RankEvalState& r = *fresh;
-      r.kind = spec.kind;
-      r.n = n;
-      r.nq = spec.num_queries;
-      r.host_label = host_label;
-      r.host_qb = spec.query_boundaries;
-      r.ks = spec.eval_at;
-      if (query) {
-        const int nq = spec.num_queries, ne = static_cast<int>(spec.eval_at.size());
-        std::vector<int> qb(spec.query_boundaries, spec.query_boundaries + nq + 1);
-        int maxq = 1;
-        for (int q = 0; q < nq; ++q) maxq = std::max(maxq, qb[q + 1] - qb[q]);
-        r.qb.Upload(qb, stream_);
-        if (spec.query_weights) r.qw.Upload(spec.query_weights, nq, stream_);
-        r.ks_dev.Upload(spec.eval_at, stream_);
-        if (spec.kind == RankMetricSpec::kNDCG) {
-          if (spec.inv_max.size() != static_cast<size_t>(nq) * ne || spec.label_gain.empty()) return false;
-          r.inv_max.Upload(spec.inv_max, stream_);
-          r.gain.Upload(spec.label_gain, stream_);
-          std::vector<double> disc(maxq);  // DCGCalculator::Init's discount table
-          for (int i = 0; i < maxq; ++i) disc[i] = 1.0 / std::log2(2.0 + i);
-          r.disc.Upload(disc, stream_);
-        } else if (spec.kind == RankMetricSpec::kMAP) {
-          if (spec.npos.size() != static_cast<size_t>(nq)) return false;
-          r.npos.Upload(spec.npos, stream_);
-        }
-        r.scratch.Resize(QueryMetricScratchBytes(n, nq, ne));
-      } else {
-        r.scratch.Resize(AucScratchBytes(n));
-      }
-      r.out.Resize(RankMetricSpec::kMaxEvalAt);
-      // the uploads' host sources (qb, disc, ...) are locals of this scope
-      HIP_CHECK(hipStreamSynchronize(stream_));
-      slot = std::move(fresh);
-    }
-    RankEvalState& r = *slot;
-    int nout = 2;
-    if (query) {
-      QueryMetricArgs qa;
-      qa.kind = spec.kind;
-      qa.qb = r.qb.get();
-      qa.nq = r.nq;
-      qa.qw = r.qw.size() ? r.qw.get() : nullptr;
-      qa.inv_max = r.inv_max.size() ? r.inv_max.get() : nullptr;
-      qa.npos = r.npos.size() ? r.npos.get() : nullptr;
-      qa.ks = r.ks_dev.get();
-      qa.ne = static_cast<int>(r.ks.size());
-      qa.gain = r.gain.size() ? r.gain.get() : nullptr;
-      qa.ngain = static_cast<int>(r.gain.size());
-      qa.disc = r.disc.size() ? r.disc.get() : nullptr;
-      LaunchQueryMetric(qa, score, label, n, r.scratch.get(), r.scratch.size(), r.out.get(), stream_);
-      nout = qa.ne;
-    } else {
-      LaunchAucMetric(spec.kind == RankMetricSpec::kAveragePrecision, score, label, weight, n, r.scratch.get(),
-                      r.scratch.size(), r.out.get(), stream_);
-    }
-    double* h = pin_metric_.Get(RankMetricSpec::kMaxEvalAt);
-    HIP_CHECK(hipMemcpyAsync(h, r.out.get(), sizeof(double) * nout, hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    out->assign(h, h + nout);
-    return true;
-  }
-
   // ---- linear-leaf trees (linear_tree=true; reference linear_tree_learner.cpp:180-360)
   // The structure comes from the frontier / sequential chain as for any tree; each leaf's
   // Gram system over the numerical features on its branch is accumulated by the fp64 MFMA
@@ -1636,18 +1289,8 @@ class DeviceTreeLearner : public TreeLearner {
     lin.feat = lin_tfeat_.get();
     lin.coef = lin_tcoef_.get();
     lin.cnst = lin_tcnst_.get();
-    lin_pending_ = &lin;
-    TraverseTreeCompact(tree, rowbins_.get(), N_, s);
-    lin_pending_ = nullptr;
+    TraverseTreeCompact(tree, rowbins_.get(), N_, s, &lin);
     HIP_CHECK(hipStreamSynchronize(stream_));
-  }
-
-  void EnsureMetricLabels() {
-    if (metric_label_.size() != 0) return;
-    const Metadata& md = data_->metadata();
-    metric_label_.Upload(md.label(), N_, stream_);  // the raw labels (objectives may relabel theirs)
-    if (md.weights()) metric_weight_.Upload(md.weights(), N_, stream_);
-    metric_partial_.Resize(kMetricBlocks + 1);
   }
 
   std::unique_ptr<Tree> DeviceTrain(int class_id, bool is_first_tree) override {
@@ -4114,7 +3757,6 @@ class DeviceTreeLearner : public TreeLearner {
   int fC_ = 0, fkmax_ = 1, fpart_tile_ = 2048, ftile_cap_ = 1, fpart_grid_ = 1, fspec_cap_ = 0, fpolicy_ = 1;
   size_t fscan_lds_ = 0;
   DevBuf<char> farena_;
-  // score update fused with the next pointwise gradients (DeviceAddTreeToScore)
   // linear-leaf trees (FitLinearLeaves / TraverseLinear)
   bool linear_ = false, lin_has_nan_ = false;
   DevBuf<float> lin_raw_;
@@ -4122,7 +3764,6 @@ class DeviceTreeLearner : public TreeLearner {
   DevBuf<int> lin_off_, lin_feats_, lin_toff_, lin_tfeat_;
   DevBuf<double> lin_partial_, lin_out_, lin_tcoef_, lin_tcnst_;
   DevBuf<long long> lin_usable_;
-  const LinearLeaves* lin_pending_ = nullptr;  // set around TraverseLinear's traversal
   // feature-parallel frontier (FrontierMode::kFeature)
   bool ffeature_ = false;
   bool fowner_ = false;  // data-parallel owner-computes rounds (FrontierMode::kDataOwner)
@@ -4363,29 +4004,6 @@ class DeviceTreeLearner : public TreeLearner {
     DevBuf<float> label, weight;
     const float* host_label = nullptr;  // the dataset's labels (identity check of metric specs)
   };
-  // per-metric device tables of the ranking / AUC metrics (DeviceEvalRank), keyed by the metric
-  struct RankEvalState {
-    int kind = -1, n = 0, nq = 0;
-    const void* host_label = nullptr;
-    const void* host_qb = nullptr;
-    std::vector<int> ks;
-    DevBuf<int> qb, npos, ks_dev;
-    DevBuf<float> qw;
-    DevBuf<double> inv_max, gain, disc, out;
-    DevBuf<char> scratch;
-  };
-  std::map<const void*, std::unique_ptr<RankEvalState>> rank_states_;
-  // auc_mu tables per metric: the class-ordered row index, one pair's scored rows, the pairs' sums
-  struct AucMuState {
-    int n = 0;
-    const void* host_label = nullptr;
-    DevBuf<int> idx;
-    DevBuf<double> dist, out;
-    DevBuf<float> lab, w;
-    DevBuf<char> scratch;
-  };
-  std::map<const void*, std::unique_ptr<AucMuState>> aucmu_states_;
-  PinnedBuf<double> pin_metric_;
   std::vector<std::unique_ptr<DevValid>> valid_;
   // refit / leaf renewal
   DevBuf<int> leaf_pred_dev_, renew_off_, renew_nz_;
@@ -4413,9 +4031,8 @@ class DeviceTreeLearner : public TreeLearner {
   int num_pos_ids_ = 0;
   double pos_lr_ = 0.0, pos_reg_ = 0.0;
   // device training metrics
-  static constexpr int kMetricBlocks = 1024;
-  DevBuf<float> metric_label_, metric_weight_;
-  DevBuf<double> metric_partial_;
+  DevBuf<float> metric_label_, metric_weight_;  // ScoreViewOf: the training set's raw labels / weights
+  MetricEval metrics_;
   XendcgArgs xendcg_args_;
   // pinned staging
   PinnedBuf<TreeParams> pin_tp_;
@@ -4428,10 +4045,7 @@ class DeviceTreeLearner : public TreeLearner {
   DevBuf<unsigned> grad_flag_;       // DeviceSetGradientsFromDevice: non-finite bits of the pass
   PinnedBuf<unsigned> pin_grad_flag_;
   PinnedBuf<char> pin_tree_;
-  PinnedBuf<char> pin_tree_ring_[2];  // TraverseTreeCompact staging (see there)
-  DevBuf<char> ttree_buf_;             // its device copy (stream-ordered reuse)
-  hipEvent_t tree_evt_[2] = {nullptr, nullptr};
-  unsigned tree_slot_ = 0;
+  StagingRing tree_ring_;  // compact trees and leaf maps of the score update (LeafMapScore, TraverseTreeCompact)
   PinnedBuf<unsigned> pin_max_;
   // device row sampling
   DevBuf<uint2> samp_jump_;

@@ -178,6 +178,27 @@ class DevBuf {
   bool owns_ = true;
 };
 
+// ---- owning pinned host buffer (grows, never shrinks)
+template <typename T>
+class PinnedBuf {
+ public:
+  ~PinnedBuf() {
+    if (p_) (void)hipHostFree(p_);
+  }
+  T* Get(size_t n) {
+    if (n > n_) {
+      if (p_) HIP_CHECK(hipHostFree(p_));
+      HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&p_), std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault));
+      n_ = n;
+    }
+    return p_;
+  }
+
+ private:
+  T* p_ = nullptr;
+  size_t n_ = 0;
+};
+
 // Bump allocator laying out many small device buffers inside ONE allocation
 // (one TLB reach for all per-tree state instead of a page per buffer).
 class ArenaLayout {

@@ -7,6 +7,8 @@
 #include <cstddef>
 #include <vector>
 
+#include "device/hip_common.h"
+
 namespace lgap {
 namespace device {
 
@@ -49,6 +51,46 @@ void AllGatherInPlace(void* buf, size_t bytes, hipStream_t stream);
 // over IPC (xGMI transport); collective; false on every rank if any rank failed
 bool XgmiOpen(char* local, std::vector<char*>* peers);
 void XgmiClose(char* local, std::vector<char*>* peers);
+
+// Two-slot staging of small per-tree uploads: the host fills one pinned buffer while the copy
+// out of the other may still be queued, so an upload returns without waiting for the GPU (the
+// next launches queue behind it instead of after a host round trip). One device copy, reused
+// in stream order.
+class StagingRing {
+ public:
+  ~StagingRing() {
+    for (auto& ev : evt_) {
+      if (ev) (void)hipEventDestroy(ev);
+    }
+  }
+  // the next slot's pinned buffer of `bytes`, after the copy last queued out of it has run
+  char* Begin(size_t bytes) {
+    slot_ = next_++ & 1;
+    if (evt_[slot_] == nullptr) HIP_CHECK(hipEventCreateWithFlags(&evt_[slot_], hipEventDisableTiming));
+    else HIP_CHECK(hipEventSynchronize(evt_[slot_]));
+    bytes_ = bytes;
+    return host_ = pin_[slot_].Get(bytes);
+  }
+  // queues the copy of what Begin handed out; returns the device copy
+  const char* Commit(hipStream_t stream) {
+    if (dev_.size() < bytes_) {
+      HIP_CHECK(hipStreamSynchronize(stream));  // queued kernels still read the old buffer
+      dev_.Resize(bytes_);
+    }
+    HIP_CHECK(hipMemcpyAsync(dev_.get(), host_, bytes_, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipEventRecord(evt_[slot_], stream));
+    return dev_.get();
+  }
+
+ private:
+  PinnedBuf<char> pin_[2];
+  DevBuf<char> dev_;
+  hipEvent_t evt_[2] = {nullptr, nullptr};
+  unsigned next_ = 0;
+  int slot_ = 0;
+  char* host_ = nullptr;
+  size_t bytes_ = 0;
+};
 
 }  // namespace device
 }  // namespace lgap

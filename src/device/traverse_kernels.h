@@ -16,26 +16,11 @@
 #include <cstdint>
 
 #include "device/leaf_kernels.h"
+#include "device/traverse_pack.h"
 #include "lgap/pointwise.h"
 
 namespace lgap {
 namespace device {
-
-struct TNode {
-  uint16_t group, lo, hi, tg;
-  int16_t gmiss;   // -1: no separate missing bin in range
-  uint8_t flags;   // bit0 out_left, bit1 default_left, bit2 categorical
-  uint8_t pad;
-  int16_t left, right;  // >= 0: node, < 0: ~leaf
-};
-static_assert(sizeof(TNode) == 16, "TNode layout");
-
-// categorical node data, indexed by node (meaningful for categorical nodes only)
-struct TCat {
-  int offset, num_bin, mfb, begin, nwords, pad;
-};
-
-constexpr uint8_t kTOutLeft = 1, kTDefaultLeft = 2, kTCat = 4;
 
 // score[i] += value of row i's leaf, rows [0, n) of the packed matrix (stride_dw dwords/row)
 // 4-bit copy of 8-bit packed rows whose every group has <= 16 bins (max_bin <= 15 data):
@@ -45,8 +30,7 @@ void LaunchPackNibbles(const uint32_t* rowbins, int stride_dw, int n, int groups
                        hipStream_t s);
 
 // width: 0 = 4-bit rows, 1 = 8-bit, 2 = 16-bit group bins
-void LaunchTraverse(const uint32_t* rowbins, int stride_dw, int width, int n, const TNode* nodes, int num_nodes,
-                    const TCat* cats, const uint32_t* cat_bits, const double* leaf_value, int num_leaves, double* score,
+void LaunchTraverse(const uint32_t* rowbins, int stride_dw, int width, int n, const CompactTreeDev& t, double* score,
                     int num_cu, hipStream_t s);
 
 // Score update from the final leaf ranges of the frontier tree just grown (reference
@@ -83,9 +67,8 @@ size_t LeafTileBoundsInts(int n, int num_leaves);
 // latency-bound: more walks in flight).
 constexpr int kLeafOobBuf = kLeafIdxBufs - 1;
 void LaunchLeafMapList(const uint8_t* colbins, const uint32_t* rowbins, int stride_dw, int width, int n,
-                       const int* list, int count, const TNode* nodes, int num_nodes, const TCat* cats,
-                       const uint32_t* cat_bits, int map_leaves, void* map, int rows_per_thread, int num_cu,
-                       hipStream_t s);
+                       const int* list, int count, const CompactTreeDev& t, int map_leaves, void* map,
+                       int rows_per_thread, int num_cu, hipStream_t s);
 void LaunchLeafMap(const LeafMapArgs& a, int* bounds, void* map, double* lv_out, hipStream_t s);
 void LaunchLeafMapAdd(const void* map, const double* lv, int num_leaves, int n, double* score, int num_cu,
                       hipStream_t s);
@@ -96,13 +79,11 @@ void LaunchLeafMapAddGrad(const void* map, const double* lv, int num_leaves, int
 // linear-leaf trees (linear_kernels.h LinearLeaves): score[i] += the leaf's linear model at
 // row i's raw values (its constant output when one of them is NaN); 8- / 16-bit rows
 struct LinearLeaves;
-void LaunchTraverseLinear(const uint32_t* rowbins, int stride_dw, int width, int n, const TNode* nodes, int num_nodes,
-                          const TCat* cats, const uint32_t* cat_bits, const double* leaf_value, int num_leaves,
+void LaunchTraverseLinear(const uint32_t* rowbins, int stride_dw, int width, int n, const CompactTreeDev& t,
                           const LinearLeaves& lin, double* score, int num_cu, hipStream_t s);
 
 // the same over the group-major copy colbins[g * n + row] (wide training rows)
-void LaunchTraverseCols(const uint8_t* colbins, int width, int n, const TNode* nodes, int num_nodes, const TCat* cats,
-                        const uint32_t* cat_bits, const double* leaf_value, int num_leaves, double* score, int num_cu,
+void LaunchTraverseCols(const uint8_t* colbins, int width, int n, const CompactTreeDev& t, double* score, int num_cu,
                         hipStream_t s);
 
 }  // namespace device

@@ -294,98 +294,92 @@ void LaunchPackNibbles(const uint32_t* rowbins, int stride_dw, int n, int groups
   HIP_CHECK(hipGetLastError());
 }
 
-void LaunchTraverseCols(const uint8_t* colbins, int width, int n, const TNode* nodes, int num_nodes, const TCat* cats,
-                        const uint32_t* cat_bits, const double* leaf_value, int num_leaves, double* score, int num_cu,
+void LaunchTraverseCols(const uint8_t* colbins, int width, int n, const CompactTreeDev& t, double* score, int num_cu,
                         hipStream_t s) {
   if (n <= 0) return;
-  const size_t lds = ((sizeof(TNode) * num_nodes + 15) & ~size_t(15)) + sizeof(double) * num_leaves;
+  const size_t lds = ((sizeof(TNode) * t.num_nodes + 15) & ~size_t(15)) + sizeof(double) * t.num_leaves;
   const int grid = std::max(1, std::min(DivUp(n, kTRows), num_cu * 8));
   if (width == 1) {
-    k_traverse_col<1><<<grid, kTThreads, lds, s>>>(colbins, n, nodes, num_nodes, cats, cat_bits, leaf_value, num_leaves,
-                                                  score);
+    k_traverse_col<1><<<grid, kTThreads, lds, s>>>(colbins, n, t.nodes, t.num_nodes, t.cats, t.cat_bits, t.leaf_value,
+                                                  t.num_leaves, score);
   } else {
-    k_traverse_col<2><<<grid, kTThreads, lds, s>>>(colbins, n, nodes, num_nodes, cats, cat_bits, leaf_value, num_leaves,
-                                                  score);
+    k_traverse_col<2><<<grid, kTThreads, lds, s>>>(colbins, n, t.nodes, t.num_nodes, t.cats, t.cat_bits, t.leaf_value,
+                                                  t.num_leaves, score);
   }
   HIP_CHECK(hipGetLastError());
 }
 
 template <typename T, int R>
 void LaunchListT(const uint8_t* colbins, const uint32_t* rowbins, int stride_dw, int width, int n, const int* list,
-                 int count, const TNode* nodes, int num_nodes, const TCat* cats, const uint32_t* cat_bits, T* map,
-                 int num_cu, hipStream_t s) {
-  const size_t lds = sizeof(TNode) * static_cast<size_t>(std::max(num_nodes, 1));
+                 int count, const CompactTreeDev& t, T* map, int num_cu, hipStream_t s) {
+  const size_t lds = sizeof(TNode) * static_cast<size_t>(std::max(t.num_nodes, 1));
   const int grid = std::max(1, std::min(DivUp(count, kTThreads * R), num_cu * 8));
   const long long stride = 4LL * stride_dw;
   if (colbins != nullptr) {
-    if (width == 1) k_traverse_list<true, 1, T, R><<<grid, kTThreads, lds, s>>>(colbins, 0, n, list, count, nodes, num_nodes, cats, cat_bits, map);
-    else k_traverse_list<true, 2, T, R><<<grid, kTThreads, lds, s>>>(colbins, 0, n, list, count, nodes, num_nodes, cats, cat_bits, map);
+    if (width == 1) k_traverse_list<true, 1, T, R><<<grid, kTThreads, lds, s>>>(colbins, 0, n, list, count, t.nodes, t.num_nodes, t.cats, t.cat_bits, map);
+    else k_traverse_list<true, 2, T, R><<<grid, kTThreads, lds, s>>>(colbins, 0, n, list, count, t.nodes, t.num_nodes, t.cats, t.cat_bits, map);
   } else {
     const uint8_t* rb = reinterpret_cast<const uint8_t*>(rowbins);
-    if (width == 1) k_traverse_list<false, 1, T, R><<<grid, kTThreads, lds, s>>>(rb, stride, n, list, count, nodes, num_nodes, cats, cat_bits, map);
-    else k_traverse_list<false, 2, T, R><<<grid, kTThreads, lds, s>>>(rb, stride, n, list, count, nodes, num_nodes, cats, cat_bits, map);
+    if (width == 1) k_traverse_list<false, 1, T, R><<<grid, kTThreads, lds, s>>>(rb, stride, n, list, count, t.nodes, t.num_nodes, t.cats, t.cat_bits, map);
+    else k_traverse_list<false, 2, T, R><<<grid, kTThreads, lds, s>>>(rb, stride, n, list, count, t.nodes, t.num_nodes, t.cats, t.cat_bits, map);
   }
 }
 
 template <typename T>
 void LaunchListR(const uint8_t* colbins, const uint32_t* rowbins, int stride_dw, int width, int n, const int* list,
-                 int count, const TNode* nodes, int num_nodes, const TCat* cats, const uint32_t* cat_bits, T* map,
-                 int rows_per_thread, int num_cu, hipStream_t s) {
-  if (rows_per_thread <= 2) LaunchListT<T, 2>(colbins, rowbins, stride_dw, width, n, list, count, nodes, num_nodes, cats, cat_bits, map, num_cu, s);
-  else if (rows_per_thread <= 4) LaunchListT<T, 4>(colbins, rowbins, stride_dw, width, n, list, count, nodes, num_nodes, cats, cat_bits, map, num_cu, s);
-  else LaunchListT<T, 8>(colbins, rowbins, stride_dw, width, n, list, count, nodes, num_nodes, cats, cat_bits, map, num_cu, s);
+                 int count, const CompactTreeDev& t, T* map, int rows_per_thread, int num_cu, hipStream_t s) {
+  if (rows_per_thread <= 2) LaunchListT<T, 2>(colbins, rowbins, stride_dw, width, n, list, count, t, map, num_cu, s);
+  else if (rows_per_thread <= 4) LaunchListT<T, 4>(colbins, rowbins, stride_dw, width, n, list, count, t, map, num_cu, s);
+  else LaunchListT<T, 8>(colbins, rowbins, stride_dw, width, n, list, count, t, map, num_cu, s);
 }
 
 void LaunchLeafMapList(const uint8_t* colbins, const uint32_t* rowbins, int stride_dw, int width, int n,
-                       const int* list, int count, const TNode* nodes, int num_nodes, const TCat* cats,
-                       const uint32_t* cat_bits, int map_leaves, void* map, int rows_per_thread, int num_cu,
-                       hipStream_t s) {
+                       const int* list, int count, const CompactTreeDev& t, int map_leaves, void* map,
+                       int rows_per_thread, int num_cu, hipStream_t s) {
   if (count <= 0) return;
   if (width != 1 && width != 2) Log::Fatal("LaunchLeafMapList: group-bin width %d (8- / 16-bit rows)", width);
   if (map_leaves <= 256) {
-    LaunchListR(colbins, rowbins, stride_dw, width, n, list, count, nodes, num_nodes, cats, cat_bits,
-                static_cast<uint8_t*>(map), rows_per_thread, num_cu, s);
+    LaunchListR(colbins, rowbins, stride_dw, width, n, list, count, t, static_cast<uint8_t*>(map), rows_per_thread,
+                num_cu, s);
   } else {
-    LaunchListR(colbins, rowbins, stride_dw, width, n, list, count, nodes, num_nodes, cats, cat_bits,
-                static_cast<uint16_t*>(map), rows_per_thread, num_cu, s);
+    LaunchListR(colbins, rowbins, stride_dw, width, n, list, count, t, static_cast<uint16_t*>(map), rows_per_thread,
+                num_cu, s);
   }
   HIP_CHECK(hipGetLastError());
 }
 
-void LaunchTraverse(const uint32_t* rowbins, int stride_dw, int width, int n, const TNode* nodes, int num_nodes,
-                    const TCat* cats, const uint32_t* cat_bits, const double* leaf_value, int num_leaves, double* score,
+void LaunchTraverse(const uint32_t* rowbins, int stride_dw, int width, int n, const CompactTreeDev& t, double* score,
                     int num_cu, hipStream_t s) {
   if (n <= 0) return;
-  const size_t lds = ((sizeof(TNode) * num_nodes + 15) & ~size_t(15)) + ((sizeof(double) * num_leaves + 15) & ~size_t(15)) +
+  const size_t lds = ((sizeof(TNode) * t.num_nodes + 15) & ~size_t(15)) + ((sizeof(double) * t.num_leaves + 15) & ~size_t(15)) +
                      (stride_dw <= kTMaxDw ? sizeof(uint32_t) * kTRows * stride_dw : 0);
   const int grid = TraverseGrid(n, num_cu);
   LinearLeaves none{};
   if (width == 0) {
-    k_traverse<0, false><<<grid, kTThreads, lds, s>>>(rowbins, stride_dw, n, nodes, num_nodes, cats, cat_bits, leaf_value,
-                                                     num_leaves, score, none);
+    k_traverse<0, false><<<grid, kTThreads, lds, s>>>(rowbins, stride_dw, n, t.nodes, t.num_nodes, t.cats, t.cat_bits,
+                                                     t.leaf_value, t.num_leaves, score, none);
   } else if (width == 1) {
-    k_traverse<1, false><<<grid, kTThreads, lds, s>>>(rowbins, stride_dw, n, nodes, num_nodes, cats, cat_bits, leaf_value,
-                                                     num_leaves, score, none);
+    k_traverse<1, false><<<grid, kTThreads, lds, s>>>(rowbins, stride_dw, n, t.nodes, t.num_nodes, t.cats, t.cat_bits,
+                                                     t.leaf_value, t.num_leaves, score, none);
   } else {
-    k_traverse<2, false><<<grid, kTThreads, lds, s>>>(rowbins, stride_dw, n, nodes, num_nodes, cats, cat_bits, leaf_value,
-                                                     num_leaves, score, none);
+    k_traverse<2, false><<<grid, kTThreads, lds, s>>>(rowbins, stride_dw, n, t.nodes, t.num_nodes, t.cats, t.cat_bits,
+                                                     t.leaf_value, t.num_leaves, score, none);
   }
   HIP_CHECK(hipGetLastError());
 }
 
-void LaunchTraverseLinear(const uint32_t* rowbins, int stride_dw, int width, int n, const TNode* nodes, int num_nodes,
-                          const TCat* cats, const uint32_t* cat_bits, const double* leaf_value, int num_leaves,
+void LaunchTraverseLinear(const uint32_t* rowbins, int stride_dw, int width, int n, const CompactTreeDev& t,
                           const LinearLeaves& lin, double* score, int num_cu, hipStream_t s) {
   if (n <= 0) return;
-  const size_t lds = ((sizeof(TNode) * num_nodes + 15) & ~size_t(15)) + ((sizeof(double) * num_leaves + 15) & ~size_t(15)) +
+  const size_t lds = ((sizeof(TNode) * t.num_nodes + 15) & ~size_t(15)) + ((sizeof(double) * t.num_leaves + 15) & ~size_t(15)) +
                      (stride_dw <= kTMaxDw ? sizeof(uint32_t) * kTRows * stride_dw : 0);
   const int grid = std::max(1, std::min(DivUp(n, kTRows), num_cu * 8));
   if (width == 1) {
-    k_traverse<1, true><<<grid, kTThreads, lds, s>>>(rowbins, stride_dw, n, nodes, num_nodes, cats, cat_bits, leaf_value,
-                                                    num_leaves, score, lin);
+    k_traverse<1, true><<<grid, kTThreads, lds, s>>>(rowbins, stride_dw, n, t.nodes, t.num_nodes, t.cats, t.cat_bits,
+                                                    t.leaf_value, t.num_leaves, score, lin);
   } else {
-    k_traverse<2, true><<<grid, kTThreads, lds, s>>>(rowbins, stride_dw, n, nodes, num_nodes, cats, cat_bits, leaf_value,
-                                                    num_leaves, score, lin);
+    k_traverse<2, true><<<grid, kTThreads, lds, s>>>(rowbins, stride_dw, n, t.nodes, t.num_nodes, t.cats, t.cat_bits,
+                                                    t.leaf_value, t.num_leaves, score, lin);
   }
   HIP_CHECK(hipGetLastError());
 }

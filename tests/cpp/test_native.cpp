@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "device/engine_plan.h"
+#include "device/traverse_pack.h"
 #include "lgap/c_api.h"
 #include "lgap/common.h"
 #include "lgap/log.h"
@@ -582,9 +583,102 @@ void TestGradientQuantizerLevels() {
   }
 }
 
+// PackCompactNode (device/traverse_pack.h) against the decision on the decoded bin, for every
+// group bin of every small feature shape. The packed decision is traverse_kernels.h's contract:
+// outside [lo, hi] `out_left`, at gmiss `default_left`, otherwise gb <= tg. The decoded decision
+// is GoLeft of split_scan.h (which the partition uses): the feature bin is the mfb outside the
+// stored range, else local < mfb ? local : local + 1; the missing bin of the node's missing type
+// takes `default_left`, every other bin goes left when it is <= the threshold.
+void TestCompactNodePredicate() {
+  using namespace lgap::device;  // NOLINT
+  long long cases = 0;
+  for (const int offset : {1, 5, 200}) {
+    for (int nb = 2; nb <= 10; ++nb) {
+      for (int mfb = 0; mfb < nb; ++mfb) {
+        for (int dbin = 0; dbin < nb; ++dbin) {
+          lgap::FeatureInfo fi;
+          fi.group = 3;
+          fi.offset = offset;
+          fi.num_bin = nb;
+          fi.mfb = static_cast<uint32_t>(mfb);
+          fi.default_bin = static_cast<uint32_t>(dbin);
+          for (int missing = 0; missing <= 2; ++missing) {
+            for (int dleft = 0; dleft <= 1; ++dleft) {
+              for (int thr = 0; thr < nb; ++thr) {
+                const int8_t dt = static_cast<int8_t>((dleft ? lgap::kDefaultLeftMask : 0) | (missing << 2));
+                TNode d;
+                TCat c;
+                PackCompactNode(fi, dt, thr, 7, ~4, 0, 0, &d, &c);
+                const int before = g_failures;
+                EXPECT(d.group == 3 && d.left == 7 && d.right == ~4 && (d.flags & kTCat) == 0);
+                EXPECT(((d.flags & kTDefaultLeft) != 0) == (dleft != 0));
+                for (int gb = 0; gb < offset + nb + 3; ++gb, ++cases) {
+                  bool packed;
+                  if (gb < d.lo || gb > d.hi) packed = (d.flags & kTOutLeft) != 0;
+                  else if (gb == d.gmiss) packed = (d.flags & kTDefaultLeft) != 0;
+                  else packed = gb <= d.tg;
+                  const int local = gb - offset;
+                  const int b = (local < 0 || local >= nb - 1) ? mfb : (local < mfb ? local : local + 1);
+                  const bool is_missing = (missing == 1 && b == dbin) || (missing == 2 && b == nb - 1);
+                  const bool decoded = is_missing ? dleft != 0 : b <= thr;
+                  EXPECT(packed == decoded);
+                }
+                if (g_failures != before) {
+                  std::fprintf(stderr, "  ^ offset %d num_bin %d mfb %d default_bin %d missing %d default_left %d thr %d\n",
+                               offset, nb, mfb, dbin, missing, dleft, thr);
+                  if (g_failures > 50) return;
+                }
+              }
+            }
+          }
+        }
+      }
+    }
+  }
+  EXPECT(cases > 4000000);  // (nothing skipped)
+
+  // a categorical node: the flag, the feature's decode data and the word range
+  {
+    lgap::FeatureInfo fi;
+    fi.group = 9;
+    fi.offset = 17;
+    fi.num_bin = 40;
+    fi.mfb = 6;
+    TNode d;
+    TCat c;
+    PackCompactNode(fi, lgap::kCategoricalMask, 2, ~0, 5, 11, 2, &d, &c);
+    EXPECT(d.flags == kTCat && d.group == 9 && d.left == ~0 && d.right == 5 && d.gmiss == -1);
+    EXPECT(c.offset == 17 && c.num_bin == 40 && c.mfb == 6 && c.begin == 11 && c.nwords == 2 && c.pad == 0);
+  }
+
+  // the staged layout: 256-byte aligned parts that add up, and the tree packed through it
+  {
+    lgap::Tree tree(32);
+    const uint32_t bits[3] = {0x5u, 0x0u, 0x80000000u};
+    for (int l = 0; l < 19; ++l) {
+      if (l == 4) tree.SplitCategorical(l, 0, 0, bits, 3, bits, 3, 0.5, -0.5, 1, 1, 1.0, 1.0, 1.f, lgap::MissingType::None);
+      else tree.Split(l, 0, 0, 1, 0.5, 0.25 * l, -0.25 * l, 1, 1, 1.0, 1.0, 1.f, lgap::MissingType::None, false);
+    }
+    const int nl = tree.num_leaves(), nn = nl - 1;
+    EXPECT(nl == 20);
+    const CompactLayout z = CompactTreeLayout(&tree);
+    EXPECT(z.cat % 256 == 0 && z.leaf % 256 == 0 && z.bit % 256 == 0);
+    EXPECT(z.cat >= sizeof(TNode) * nn && z.leaf - z.cat >= sizeof(TCat) * nn && z.bit - z.leaf >= sizeof(double) * nl);
+    EXPECT(z.cat < sizeof(TNode) * nn + 256 && z.leaf - z.cat < sizeof(TCat) * nn + 256 &&
+           z.bit - z.leaf < sizeof(double) * nl + 256);
+    EXPECT(z.total == z.bit + sizeof(uint32_t) * tree.cat_threshold_inner().size());
+    const CompactTreeDev t = CompactTreeAt(static_cast<const char*>(nullptr) + 4096, z, nl);
+    EXPECT(reinterpret_cast<const char*>(t.cats) - reinterpret_cast<const char*>(t.nodes) == static_cast<long>(z.cat));
+    EXPECT(reinterpret_cast<const char*>(t.leaf_value) - reinterpret_cast<const char*>(t.nodes) == static_cast<long>(z.leaf));
+    EXPECT(reinterpret_cast<const char*>(t.cat_bits) - reinterpret_cast<const char*>(t.nodes) == static_cast<long>(z.bit));
+    EXPECT(t.num_nodes == nn && t.num_leaves == nl);
+  }
+}
+
 int main(int argc, char** argv) {
   const std::string data = argc > 1 ? argv[1] : "tests/data";
   TestEnginePlan();
+  TestCompactNodePredicate();
   TestGradientQuantizerLevels();
   TestRandom();
   TestCommon();
