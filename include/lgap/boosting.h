@@ -80,7 +80,7 @@ class GBDT {
   virtual bool TrainOneIter(const score_t* gradients, const score_t* hessians);
   // one iteration from a custom objective's gradients in device memory (fatal unless the
   // booster is device-resident and has no built-in objective)
-  bool TrainOneIterDevice(const DeviceGradView& view);
+  virtual bool TrainOneIterDevice(const DeviceGradView& view);
   void Train(int snapshot_freq, const std::string& model_output_path);
   virtual void RollbackOneIter();
   bool EvalAndCheckEarlyStopping();
@@ -160,8 +160,9 @@ class GBDT {
   void SyncTrainScoreFromDevice();
   void ResetGradientBuffers();
   std::vector<double> EvalTraining(const Metric* m, const double** score);
-  // DART drops trees when the training score is first read in an iteration: keep that read
-  virtual bool DeviceMetricsAllowed() const { return true; }
+  // DART drops trees when the training score is first read in an iteration; reads that bypass
+  // GetTrainingScore (metrics evaluated on the device, raw_score_device) call this first
+  virtual void BeforeTrainingScoreRead() {}
   std::vector<double> EvalOne(const Metric* m, const double* score) const;
 
   const Config* config_ = nullptr;
@@ -213,14 +214,19 @@ class DART : public GBDT {
   void Init(const Config* config, const Dataset* train_data, const ObjectiveFunction* objective,
             const std::vector<const Metric*>& training_metrics) override;
   bool TrainOneIter(const score_t* gradients, const score_t* hessians) override;
+  bool TrainOneIterDevice(const DeviceGradView& view) override;  // refused
   const double* GetTrainingScore(int64_t* out_len) override;
-  bool DeviceMetricsAllowed() const override { return false; }
   const char* SubModelName() const override { return "tree"; }
+
+ protected:
+  void BeforeTrainingScoreRead() override;
 
  private:
   bool updated_cur_iter_ = false;
   void DroppingTrees();
   void Normalize();
+  std::vector<TreeRef> DroppedTrees() const;
+  void AddTreesToTrainingScore(const std::vector<TreeRef>& trees);
   Random random_for_drop_;
   std::vector<double> tree_weight_;
   double sum_weight_ = 0.0;

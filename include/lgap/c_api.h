@@ -377,6 +377,19 @@ LIGHTGBM_C_EXPORT int LGBM_DeviceTestLinearGram(const float* raw, int32_t num_da
                                                 int32_t num_rows, const int32_t* segs, int num_leaves,
                                                 const int32_t* feat_off, const int32_t* feats, int chunks,
                                                 double* out, int64_t* out_usable);
+// The forest traversal (k_traverse_forest) with a device learner on the Dataset: trees
+// tree_idx[0 .. num_trees) of the booster, tree j's leaf values times scales[j] (Tree::Shrinkage on
+// a copy), are added in list order into a copy of score [num_data], returned in out. grid > 0 caps
+// the kernel's grid; per_tree != 0 runs one single-tree traversal per tree instead. out_info (may
+// be null) [2]: the group-bin width of the rows read (0 = 4-bit rows, 1, 2 bytes), dwords per row.
+LIGHTGBM_C_EXPORT int LGBM_DeviceTestForestScore(DatasetHandle handle, BoosterHandle booster, const int32_t* tree_idx,
+                                                 const double* scales, int num_trees, const double* score, int grid,
+                                                 int per_tree, double* out, int32_t* out_info);
+// How that forest is split into LDS runs (no GPU needed): out_run_trees [num_trees] the trees per
+// run, out_run_bytes [num_trees] their bytes, *out_num_runs, and *out_budget the run byte budget.
+LIGHTGBM_C_EXPORT int LGBM_DeviceTestForestRuns(BoosterHandle booster, const int32_t* tree_idx, int num_trees,
+                                                int32_t* out_run_trees, int32_t* out_run_bytes, int* out_num_runs,
+                                                int* out_budget);
 // One device row-sampling pass (the HIP bagging / GOSS kernels) over host arrays: mode 1 bagging,
 // 2 balanced bagging, 3 GOSS; `rounds` > 1 re-bags with the advanced streams and reports the last.
 // grad/hess (num_class * num_rows, class-major) are scaled in place by GOSS. Returns the kept

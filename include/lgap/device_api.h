@@ -109,6 +109,13 @@ void TestFrontierPartition(const Dataset* data, const Config& config, const int*
 bool TestQuantize(const Dataset* data, const Config& config, bool const_hess, const float* grad, const float* hess,
                   int num_class, int rounds, float* out_gh, uint16_t* out_levels, uint32_t* out_qmax,
                   float* out_true);
+// Direct test of the forest traversal (tests/test_traverse_forest_kernel.py): a device learner of
+// `config` on `data` with `score` [N] as its one-class training score; copies of the trees scaled
+// by Tree::Shrinkage(scales[i]) are added in list order by one k_traverse_forest launch (grid_cap
+// > 0 caps its grid), or with per_tree by one single-tree traversal each -> out[N]. info (may be
+// null): {group-bin width of the rows read (0 = 4-bit rows, 1, 2 bytes), dwords per row}.
+void TestForestScore(const Dataset* data, const Config& config, const Tree* const* trees, const double* scales,
+                     int count, const double* score, int grid_cap, bool per_tree, double* out, int* info);
 // Direct test of the linear-leaf Gram kernels (tests/test_linear_gram_kernel.py), no Dataset:
 // raw[N][F], grad / hess[N]; leaf l reads segs[3 l ..] = (buffer, start, count): buffer 0 the
 // positions [start, start + count) of rows[num_rows], buffer -1 the rows start .. start + count

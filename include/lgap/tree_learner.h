@@ -30,6 +30,19 @@ enum DeviceSamplePlan {
   kSampleBagQuery = 4,   // bagging by query (whole queries kept or dropped)
 };
 
+// A tree and the class whose score it belongs to (DeviceAddTreesToScore / DeviceAddTreesToValid)
+struct TreeRef {
+  const Tree* tree;
+  int class_id;
+};
+
+// LGAP_DEVICE_DART, read once: how boosting=dart trains on a learner that owns the score.
+// unset / "tree": the score stays on the device, one single-tree traversal per dropped tree;
+// "forest": on the device, the dropped trees rescored by one forest traversal per class; "0":
+// score and objective on the host. Any other value is fatal.
+enum class DeviceDart { kTree, kForest, kHost };
+DeviceDart DeviceDartMode();
+
 // Gradients and hessians of one boosting round as two arrays in device memory
 // (Booster.update_device). Value (row i, class k) of an array is ptr[i * row_stride +
 // k * class_stride], strides in elements; each array is fp32 or fp64.
@@ -80,6 +93,10 @@ class TreeLearner {
   virtual int DeviceId() const { return -1; }
   virtual std::unique_ptr<Tree> DeviceTrain(int class_id, bool is_first_tree) { (void)class_id; (void)is_first_tree; return nullptr; }
   virtual void DeviceAddTreeToScore(const Tree*, int class_id) { (void)class_id; }
+  // Several trees at once (DART's dropped trees): every row adds its class's trees in list
+  // order, as `count` DeviceAddTreeToScore / DeviceAddTreeToValid calls would
+  virtual void DeviceAddTreesToScore(const TreeRef* /*trees*/, int /*count*/) {}
+  virtual void DeviceAddTreesToValid(int /*id*/, const TreeRef* /*trees*/, int /*count*/) {}
   // pointwise metric from the device-resident score of class k of the training set (id < 0) or
   // of device validation set `id`: the weighted loss sum (false: evaluate on the host)
   virtual bool DeviceEvalPointwise(int /*id*/, const PwMetricParams&, int /*k*/, double* /*sum*/) { return false; }

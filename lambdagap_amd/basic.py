@@ -1264,8 +1264,8 @@ class Booster:
 
         Host arrays raise ``TypeError`` and wrong shapes ``ValueError``; a value that is not
         finite as float32, a booster whose score does not live on the GPU (``device_type=cpu``,
-        DART, random forest, a configuration routed to the host learners) and a built-in
-        objective raise the library's error. Nothing falls back to the host path: use ``update``.
+        random forest, a configuration routed to the host learners), ``boosting=dart`` and a
+        built-in objective raise the library's error. Nothing falls back to the host path: use ``update``.
         Returns True when no further split was possible, like ``update``.
         """
         if train_set is not None and train_set is not self.train_set:

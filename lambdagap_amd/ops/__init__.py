@@ -14,7 +14,8 @@ import numpy as np
 from ..basic import _LIB, Booster, Dataset, _check
 
 __all__ = ["group_layout", "group_bins", "device_histogram", "device_sample_rows", "booster_gradients",
-           "frontier_histogram", "frontier_partition", "quantize_gradients", "linear_gram"]
+           "frontier_histogram", "frontier_partition", "quantize_gradients", "linear_gram", "forest_score",
+           "forest_runs"]
 
 
 def group_layout(ds: Dataset) -> Tuple[int, int, int, np.ndarray]:
@@ -261,3 +262,51 @@ def linear_gram(raw: np.ndarray, grad: np.ndarray, hess: np.ndarray, leaves, fea
         off.ctypes.data_as(i32), flat.ctypes.data_as(i32), ctypes.c_int(chunks),
         out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), usable.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
     return out, usable
+
+
+def forest_score(ds: Dataset, booster: Booster, trees, scales, score: np.ndarray, grid: Optional[int] = None,
+                 mode: str = "forest", info: Optional[dict] = None) -> np.ndarray:
+    """The forest traversal kernel (k_traverse_forest) over the packed rows of a constructed Dataset.
+
+    For tree ``trees[j]`` of ``booster`` its leaf values times ``scales[j]`` (the fp64 product of
+    ``Tree::Shrinkage``) are added, in list order, into a copy of ``score`` (float64, num_data), which
+    is returned. ``mode="tree"`` runs one single-tree traversal per tree instead; ``grid`` caps the
+    forest kernel's grid, so one block owns several row tiles at small row counts. A dict passed as
+    ``info`` receives the row format the traversal read: ``row_bits`` (4, 8 or 16 per group bin) and
+    ``stride_dw`` (dwords per row)."""
+    if mode not in ("forest", "tree"):
+        raise ValueError(f"mode must be 'forest' or 'tree', got {mode!r}")
+    ds.construct()
+    idx = np.ascontiguousarray(trees, dtype=np.int32).ravel()
+    sc = np.ascontiguousarray(scales, dtype=np.float64).ravel()
+    if idx.size != sc.size:
+        raise ValueError("one scale per tree")
+    s = np.ascontiguousarray(score, dtype=np.float64).ravel()
+    if s.size != ds.num_data():
+        raise ValueError(f"score has {s.size} values for {ds.num_data()} rows")
+    out = np.zeros(max(s.size, 1), dtype=np.float64)
+    fmt = np.zeros(2, dtype=np.int32)
+    dp = ctypes.POINTER(ctypes.c_double)
+    _check(_LIB.LGBM_DeviceTestForestScore(
+        ds.handle, booster.handle, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), sc.ctypes.data_as(dp),
+        ctypes.c_int(idx.size), s.ctypes.data_as(dp), ctypes.c_int(int(grid or 0)),
+        ctypes.c_int(1 if mode == "tree" else 0), out.ctypes.data_as(dp),
+        fmt.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    if info is not None:
+        info["row_bits"] = (4, 8, 16)[int(fmt[0])]
+        info["stride_dw"] = int(fmt[1])
+    return out[:s.size]
+
+
+def forest_runs(booster: Booster, trees) -> Tuple[list, list, int]:
+    """How ``forest_score`` splits these trees into LDS runs: (trees per run, bytes per run, the run
+    byte budget). A run over the budget is one tree that the kernel walks from global memory."""
+    idx = np.ascontiguousarray(trees, dtype=np.int32).ravel()
+    cnt = np.zeros(max(idx.size, 1), dtype=np.int32)
+    nbytes = np.zeros(max(idx.size, 1), dtype=np.int32)
+    nruns, budget = ctypes.c_int(0), ctypes.c_int(0)
+    i32 = ctypes.POINTER(ctypes.c_int32)
+    _check(_LIB.LGBM_DeviceTestForestRuns(booster.handle, idx.ctypes.data_as(i32), ctypes.c_int(idx.size),
+                                          cnt.ctypes.data_as(i32), nbytes.ctypes.data_as(i32), ctypes.byref(nruns),
+                                          ctypes.byref(budget)))
+    return cnt[:nruns.value].tolist(), nbytes[:nruns.value].tolist(), budget.value

@@ -106,7 +106,7 @@ void GBDT::AddValidDataset(const Dataset* valid, const std::vector<const Metric*
   // pointwise metrics evaluated there, the host copy is refreshed only when read
   int dev = -1;
   const char* ev = std::getenv("LGAP_DEVICE_VALID");  // "0": score validation sets on the host
-  if (device_mode_ && DeviceMetricsAllowed() && !(ev && std::strcmp(ev, "0") == 0)) {
+  if (device_mode_ && !(ev && std::strcmp(ev, "0") == 0)) {
     dev = learner_->DeviceAddValidSet(valid, valid_score_.back());
   }
   valid_dev_.push_back(dev);
@@ -143,7 +143,7 @@ void GBDT::ResetTrainingData(const Dataset* train_data, const ObjectiveFunction*
   if (device_mode_) learner_->DeviceInitScore(train_score_, num_tree_per_iteration_);
   // register the validation sets with the new learner (device scoring where it applies)
   const char* ev = std::getenv("LGAP_DEVICE_VALID");
-  const bool dev_ok = device_mode_ && DeviceMetricsAllowed() && !(ev && std::strcmp(ev, "0") == 0);
+  const bool dev_ok = device_mode_ && !(ev && std::strcmp(ev, "0") == 0);
   for (size_t d = 0; d < valid_dev_.size(); ++d) {
     valid_dev_[d] = dev_ok ? learner_->DeviceAddValidSet(valid_data_[d], valid_score_[d]) : -1;
     valid_stale_[d] = 0;
@@ -239,7 +239,10 @@ void GBDT::UpdateScore(const Tree* tree, int k) {
     train_score_stale_ = true;
   } else {
     double* s = train_score_.data() + static_cast<size_t>(k) * num_data_;
-    if (sampler_->active()) {
+    // a host learner adds the in-bag rows from its partition, the out-of-bag rows walk the tree;
+    // a device learner scored on the host (boosting=rf, DART with LGAP_DEVICE_DART=0 or linear
+    // leaves) walks every row itself, so a second pass over the out-of-bag rows would add the tree twice
+    if (sampler_->active() && !learner_->OwnsScore()) {
       learner_->AddPredictionToScore(tree, s);
       const auto& bag = sampler_->bag_indices();
       const data_size_t bc = sampler_->bag_cnt();
@@ -426,25 +429,26 @@ std::vector<double> GBDT::EvalTraining(const Metric* m, const double** score) {
   PwMetricParams p;
   const char* off = std::getenv("LGAP_DEVICE_METRICS");  // "0": always evaluate on the host (A/B, tests)
   const bool allow = off == nullptr || std::strcmp(off, "0") != 0;
-  if (allow && device_mode_ && num_tree_per_iteration_ == 1 && DeviceMetricsAllowed() &&
-      m->DevicePointwise(objective_, &p)) {
+  // a metric evaluated on the device is a read of the training score too (DART drops then)
+  if (allow && device_mode_) BeforeTrainingScoreRead();
+  if (allow && device_mode_ && num_tree_per_iteration_ == 1 && m->DevicePointwise(objective_, &p)) {
     double sum = 0.0;
     if (learner_->DeviceEvalPointwise(-1, p, 0, &sum)) return m->FinishSum(sum);
   }
   // ranking / AUC metrics: sorted on the device, only their sums come back
   RankMetricSpec rs;
-  if (allow && device_mode_ && num_tree_per_iteration_ == 1 && DeviceMetricsAllowed() && m->DeviceRankSpec(&rs)) {
+  if (allow && device_mode_ && num_tree_per_iteration_ == 1 && m->DeviceRankSpec(&rs)) {
     std::vector<double> raw;
     if (learner_->DeviceEvalRank(-1, rs, 0, &raw)) return m->FinishRank(raw);
   }
   // multiclass logloss / error: the class-major device score, only the loss sum comes back
   MultiMetricParams mp;
-  if (allow && device_mode_ && num_tree_per_iteration_ > 1 && DeviceMetricsAllowed() && m->DeviceMulti(objective_, &mp)) {
+  if (allow && device_mode_ && num_tree_per_iteration_ > 1 && m->DeviceMulti(objective_, &mp)) {
     double sum = 0.0;
     if (learner_->DeviceEvalMulti(-1, mp, &sum)) return m->FinishSum(sum);
   }
   AucMuSpec am;
-  if (allow && device_mode_ && num_tree_per_iteration_ > 1 && DeviceMetricsAllowed() && m->DeviceAucMu(&am)) {
+  if (allow && device_mode_ && num_tree_per_iteration_ > 1 && m->DeviceAucMu(&am)) {
     std::vector<double> s;
     if (learner_->DeviceEvalAucMu(-1, am, &s)) return m->FinishAucMu(s);
   }
@@ -602,6 +606,7 @@ void GBDT::GetRawScoreDevice(int data_idx, int64_t* out_len, int* out_device, do
   if (out_device != nullptr) *out_device = learner_->DeviceId();
   if (out_dev == nullptr) return;
   if (data_idx == 0) {
+    BeforeTrainingScoreRead();
     learner_->DeviceCopyScoreTo(-1, out_dev, len);
     return;
   }
@@ -696,10 +701,52 @@ void DART::Init(const Config* config, const Dataset* train_data, const Objective
   random_for_drop_ = Random(config->drop_seed);
   sum_weight_ = 0.0;
   tree_weight_.clear();
-  if (device_mode_) {
-    // DART rewrites old trees' contributions every iteration: keep the score on host.
+  // The learner's device score is kept: the dropped trees are rescored there (DroppingTrees /
+  // Normalize). Linear leaves need the raw values on the host, and LGAP_DEVICE_DART=0 asks for
+  // the host score.
+  if (device_mode_ && (config->linear_tree || DeviceDartMode() == DeviceDart::kHost)) {
     device_mode_ = false;
+    Log::Info("DART: the score and the objective stay on the host (%s)",
+              config->linear_tree ? "linear_tree" : "LGAP_DEVICE_DART=0");
   }
+}
+
+bool DART::TrainOneIterDevice(const DeviceGradView&) {
+  Log::Fatal("update_device does not serve boosting=dart (the trees dropped in an iteration are chosen when the "
+             "score is first read); use Booster.update(fobj=...) here");
+  return true;
+}
+
+void DART::BeforeTrainingScoreRead() {
+  // dropping happens when the score is first read in an iteration (dart.hpp GetTrainingScore)
+  if (!updated_cur_iter_) {
+    DroppingTrees();
+    updated_cur_iter_ = true;
+  }
+}
+
+// every row adds its class's trees in list order, into the training score
+void DART::AddTreesToTrainingScore(const std::vector<TreeRef>& trees) {
+  if (trees.empty()) return;
+  if (device_mode_) {
+    learner_->DeviceAddTreesToScore(trees.data(), static_cast<int>(trees.size()));
+    train_score_stale_ = true;
+    return;
+  }
+  for (const TreeRef& r : trees) {
+    r.tree->AddPredictionToScore(*train_data_, num_data_, train_score_.data() + static_cast<size_t>(r.class_id) * num_data_);
+  }
+}
+
+// the dropped trees, iteration ascending, then class
+std::vector<TreeRef> DART::DroppedTrees() const {
+  std::vector<TreeRef> out;
+  for (int i : drop_index_) {
+    for (int k = 0; k < num_tree_per_iteration_; ++k) {
+      out.push_back({models_[static_cast<size_t>(i) * num_tree_per_iteration_ + k].get(), k});
+    }
+  }
+  return out;
 }
 
 void DART::DroppingTrees() {
@@ -730,13 +777,9 @@ void DART::DroppingTrees() {
       }
     }
   }
-  for (int i : drop_index_) {
-    for (int k = 0; k < num_tree_per_iteration_; ++k) {
-      Tree* t = models_[static_cast<size_t>(i) * num_tree_per_iteration_ + k].get();
-      t->Shrinkage(-1.0);
-      t->AddPredictionToScore(*train_data_, num_data_, train_score_.data() + static_cast<size_t>(k) * num_data_);
-    }
-  }
+  const std::vector<TreeRef> dropped = DroppedTrees();
+  for (const TreeRef& r : dropped) const_cast<Tree*>(r.tree)->Shrinkage(-1.0);
+  AddTreesToTrainingScore(dropped);
   if (!config_->xgboost_dart_mode) {
     shrinkage_rate_ = config_->learning_rate / (1.0 + static_cast<double>(drop_index_.size()));
   } else {
@@ -747,22 +790,30 @@ void DART::DroppingTrees() {
 
 void DART::Normalize() {
   const double k = static_cast<double>(drop_index_.size());
-  for (int i : drop_index_) {
-    for (int c = 0; c < num_tree_per_iteration_; ++c) {
-      Tree* t = models_[static_cast<size_t>(i) * num_tree_per_iteration_ + c].get();
-      if (!config_->xgboost_dart_mode) {
-        t->Shrinkage(1.0 / (k + 1.0));
-      } else {
-        t->Shrinkage(shrinkage_rate_);
-      }
-      for (size_t d = 0; d < valid_score_.size(); ++d) {
-        const data_size_t n = valid_data_[d]->num_data();
-        t->AddPredictionToScore(*valid_data_[d], n, valid_score_[d].data() + static_cast<size_t>(c) * n);
-      }
-      t->Shrinkage(!config_->xgboost_dart_mode ? -k : -k / config_->learning_rate);
-      t->AddPredictionToScore(*train_data_, num_data_, train_score_.data() + static_cast<size_t>(c) * num_data_);
+  const std::vector<TreeRef> dropped = DroppedTrees();
+  if (dropped.empty()) return;
+  // the trees at the weight they have from now on, into every validation set (which never saw
+  // the drop); then at minus what the training score still lacks of them
+  for (const TreeRef& r : dropped) {
+    const_cast<Tree*>(r.tree)->Shrinkage(!config_->xgboost_dart_mode ? 1.0 / (k + 1.0) : shrinkage_rate_);
+  }
+  for (size_t d = 0; d < valid_score_.size(); ++d) {
+    if (valid_dev_[d] >= 0) {
+      learner_->DeviceAddTreesToValid(valid_dev_[d], dropped.data(), static_cast<int>(dropped.size()));
+      valid_stale_[d] = 1;
+      continue;
     }
-    if (!config_->uniform_drop) {
+    const data_size_t n = valid_data_[d]->num_data();
+    for (const TreeRef& r : dropped) {
+      r.tree->AddPredictionToScore(*valid_data_[d], n, valid_score_[d].data() + static_cast<size_t>(r.class_id) * n);
+    }
+  }
+  for (const TreeRef& r : dropped) {
+    const_cast<Tree*>(r.tree)->Shrinkage(!config_->xgboost_dart_mode ? -k : -k / config_->learning_rate);
+  }
+  AddTreesToTrainingScore(dropped);
+  if (!config_->uniform_drop) {
+    for (int i : drop_index_) {
       const int w = i - num_init_models_ / num_tree_per_iteration_;
       if (!config_->xgboost_dart_mode) {
         sum_weight_ -= tree_weight_[w] * (1.0 / (k + 1.0));
@@ -776,19 +827,14 @@ void DART::Normalize() {
 }
 
 const double* DART::GetTrainingScore(int64_t* out_len) {
-  // dropping happens when the score is first read in an iteration (dart.hpp GetTrainingScore)
-  if (!updated_cur_iter_) {
-    DroppingTrees();
-    updated_cur_iter_ = true;
-  }
+  BeforeTrainingScoreRead();
   return GBDT::GetTrainingScore(out_len);
 }
 
 bool DART::TrainOneIter(const score_t* gradients, const score_t* hessians) {
-  if (gradients != nullptr && !updated_cur_iter_) {
-    int64_t len;
-    GetTrainingScore(&len);
-  }
+  // custom gradients were computed from a score that had the drop applied; a built-in objective
+  // on the device never reads the score through GetTrainingScore: drop before its gradient pass
+  if (gradients != nullptr || device_mode_) BeforeTrainingScoreRead();
   const bool ret = GBDT::TrainOneIter(gradients, hessians);
   updated_cur_iter_ = false;
   if (ret) return ret;

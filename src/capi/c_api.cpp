@@ -22,6 +22,7 @@
 #include "device/contrib_kernels.h"
 #include "device/contrib_pack.h"
 #include "device/predict_pack.h"
+#include "device/traverse_pack.h"
 #include "lgap/arrow.h"
 #include "lgap/boosting.h"
 #include "lgap/common.h"
@@ -1502,6 +1503,43 @@ int LGBM_DeviceTestLinearGram(const float* raw, int32_t num_data, int32_t num_fe
   static_assert(sizeof(long long) == sizeof(int64_t), "usable counts are 64-bit");
   device::TestLinearGram(raw, num_data, num_feature, grad, hess, rows, num_rows, segs, num_leaves, feat_off, feats,
                          chunks, out, reinterpret_cast<long long*>(out_usable));
+  API_END();
+}
+
+// Direct test of the forest traversal (device_api.h TestForestScore) and its run split
+static std::vector<const Tree*> ForestTreesOf(BoosterHandle booster, const int32_t* tree_idx, int num_trees) {
+  GBDT* g = B(booster)->boosting_.get();
+  std::vector<const Tree*> trees;
+  for (int i = 0; i < num_trees; ++i) {
+    if (tree_idx[i] < 0 || tree_idx[i] >= g->NumberOfTotalModel()) Log::Fatal("forest test: tree %d of %d", tree_idx[i], g->NumberOfTotalModel());
+    trees.push_back(g->GetTree(tree_idx[i]));
+  }
+  return trees;
+}
+
+int LGBM_DeviceTestForestScore(DatasetHandle handle, BoosterHandle booster, const int32_t* tree_idx,
+                               const double* scales, int num_trees, const double* score, int grid, int per_tree,
+                               double* out, int32_t* out_info) {
+  API_BEGIN();
+  Config cfg = ParseConfig("");
+  cfg.device_type = "gpu";
+  const std::vector<const Tree*> trees = ForestTreesOf(booster, tree_idx, num_trees);
+  device::TestForestScore(D(handle)->ds.get(), cfg, trees.data(), scales, num_trees, score, grid, per_tree != 0, out,
+                          out_info);
+  API_END();
+}
+
+int LGBM_DeviceTestForestRuns(BoosterHandle booster, const int32_t* tree_idx, int num_trees, int32_t* out_run_trees,
+                              int32_t* out_run_bytes, int* out_num_runs, int* out_budget) {
+  API_BEGIN();
+  const std::vector<const Tree*> trees = ForestTreesOf(booster, tree_idx, num_trees);
+  const device::ForestLayout z = device::CompactForestLayout(trees.data(), num_trees);
+  for (size_t r = 0; r < z.runs.size(); ++r) {
+    out_run_trees[r] = z.runs[r].count;
+    out_run_bytes[r] = static_cast<int32_t>(z.runs[r].bytes);
+  }
+  *out_num_runs = static_cast<int>(z.runs.size());
+  *out_budget = device::kForestRunBytes;
   API_END();
 }
 

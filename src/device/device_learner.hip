@@ -944,6 +944,76 @@ class DeviceTreeLearner : public TreeLearner {
     TraverseTree(tree, rowbins_.get(), N_, s);
   }
 
+  // Several trees into the training score (DART's dropped trees), each row adding its class's
+  // trees in list order: one single-tree traversal per tree, or with LGAP_DEVICE_DART=forest one
+  // k_traverse_forest launch per class.
+  void DeviceAddTreesToScore(const TreeRef* trees, int count) override {
+    ScopedTimer timer("Device::AddTreesToScore");
+    FlushScore();  // the last tree's deferred leaf add lands before any drop
+    AddTrees(trees, count, -1, DeviceDartMode() == DeviceDart::kTree, false, 0);
+  }
+  void DeviceAddTreesToValid(int id, const TreeRef* trees, int count) override {
+    ScopedTimer timer("Device::AddTreesToValid");
+    AddTrees(trees, count, id, DeviceDartMode() == DeviceDart::kTree, false, 0);
+  }
+
+  // id < 0: the training score, else device validation set `id`. per_tree, a linear tree or a
+  // tree past the compact node format: the single-tree path for every tree, in order. Else one
+  // k_traverse_forest launch per class over that class's trees (a lone tree takes the
+  // single-tree path unless always_forest: the kernel test).
+  void AddTrees(const TreeRef* trees, int count, int id, bool per_tree, bool always_forest, int grid_cap) {
+    for (int i = 0; i < count; ++i) per_tree |= trees[i].tree->is_linear() || trees[i].tree->num_leaves() > 32768;
+    if (per_tree) {
+      for (int i = 0; i < count; ++i) AddOneTree(trees[i].tree, trees[i].class_id, id);
+      return;
+    }
+    std::vector<const Tree*>& list = forest_list_;
+    for (int k = 0; k < K_; ++k) {
+      list.clear();
+      for (int i = 0; i < count; ++i) {
+        if (trees[i].class_id == k) list.push_back(trees[i].tree);
+      }
+      if (list.empty()) continue;
+      if (list.size() == 1 && !always_forest) {
+        AddOneTree(list[0], k, id);
+        continue;
+      }
+      const ForestLayout z = CompactForestLayout(list.data(), static_cast<int>(list.size()));
+      PackCompactForest(list.data(), data_, tree_ring_.Begin(z.total), z);
+      const ForestDev f = CompactForestAt(tree_ring_.Commit(stream_), z);
+      if (id < 0) {
+        double* s = score_.get() + static_cast<size_t>(k) * N_;
+        if (nib_) LaunchTraverseForest(rowbins4_.get(), stride4_dw_, 0, N_, f, s, num_cu_, grid_cap, stream_);
+        else LaunchTraverseForest(rowbins_.get(), tstride_dw_, width_, N_, f, s, num_cu_, grid_cap, stream_);
+      } else {
+        DevValid& v = *valid_[id];
+        LaunchTraverseForest(v.rowbins.get(), stride_dw_, width_, v.n, f, v.score.get() + static_cast<size_t>(k) * v.n,
+                             num_cu_, grid_cap, stream_);
+      }
+    }
+  }
+  void AddOneTree(const Tree* tree, int k, int id) {
+    if (id < 0) DeviceAddTreeToScore(tree, k);
+    else DeviceAddTreeToValid(id, tree, k);
+  }
+
+  // ops.forest_score: `score` (N_ values) uploaded as a one-class training score, the trees added
+  // by k_traverse_forest (per_tree: the single-tree loop), the score read back
+  // info (optional): the row format the training-set traversal reads, {group-bin width (0 = 4-bit
+  // rows, 1, 2 bytes), dwords per row}
+  void TestForestScore(const std::vector<TreeRef>& trees, const double* score, int grid_cap, bool per_tree, double* out,
+                       int* info) {
+    if (info != nullptr) {
+      info[0] = nib_ ? 0 : width_;
+      info[1] = nib_ ? stride4_dw_ : tstride_dw_;
+    }
+    DeviceInitScore(std::vector<double>(score, score + N_), 1);
+    AddTrees(trees.data(), static_cast<int>(trees.size()), -1, per_tree, true, grid_cap);
+    std::vector<double> res;
+    DeviceGetScore(&res);
+    std::copy(res.begin(), res.end(), out);
+  }
+
   // Score update from the leaf ranges of the frontier tree just grown (traverse_kernels.h
   // LaunchLeafMap): every trained row sits in exactly one leaf's index segment, so the rows'
   // leaves come from those segments instead of a walk of the tree over the packed rows. A
@@ -4046,6 +4116,7 @@ class DeviceTreeLearner : public TreeLearner {
   PinnedBuf<unsigned> pin_grad_flag_;
   PinnedBuf<char> pin_tree_;
   StagingRing tree_ring_;  // compact trees and leaf maps of the score update (LeafMapScore, TraverseTreeCompact)
+  std::vector<const Tree*> forest_list_;  // one class's trees of an AddTrees call
   PinnedBuf<unsigned> pin_max_;
   // device row sampling
   DevBuf<uint2> samp_jump_;
@@ -4233,6 +4304,24 @@ void TestFrontierPartition(const Dataset* data, const Config& config, const int*
   DeviceTreeLearner learner(&config, "serial");
   learner.Init(data, false);
   learner.TestFrontierPartition(rows, offsets, k, feats, thr, dleft, catbits, out_rows, out_left, exp_rows, exp_left);
+}
+
+void TestForestScore(const Dataset* data, const Config& config, const Tree* const* trees, const double* scales,
+                     int count, const double* score, int grid_cap, bool per_tree, double* out, int* info) {
+  if (DeviceCount() <= 0) Log::Fatal("TestForestScore: no AMD GPU visible to HIP");
+  if (count < 0 || grid_cap < 0) Log::Fatal("TestForestScore: %d trees, grid %d", count, grid_cap);
+  DeviceTreeLearner learner(&config, "serial");
+  learner.Init(data, false);
+  // the scaled copies (Tree::Shrinkage: leaf value * scale in fp64 on the host)
+  std::vector<std::unique_ptr<Tree>> own;
+  std::vector<TreeRef> refs;
+  for (int i = 0; i < count; ++i) {
+    if (trees[i]->is_linear()) Log::Fatal("TestForestScore: tree %d has linear leaves", i);
+    own.push_back(std::make_unique<Tree>(*trees[i]));
+    own.back()->Shrinkage(scales[i]);
+    refs.push_back({own.back().get(), 0});
+  }
+  learner.TestForestScore(refs, score, grid_cap, per_tree, out, info);
 }
 
 bool TestQuantize(const Dataset* data, const Config& config, bool const_hess, const float* grad, const float* hess,

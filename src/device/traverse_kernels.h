@@ -33,6 +33,13 @@ void LaunchPackNibbles(const uint32_t* rowbins, int stride_dw, int n, int groups
 void LaunchTraverse(const uint32_t* rowbins, int stride_dw, int width, int n, const CompactTreeDev& t, double* score,
                     int num_cu, hipStream_t s);
 
+// A forest (traverse_pack.h PackCompactForest) in one pass over the rows: score[i] = (((score[i]
+// + T_0(i)) + T_1(i)) + ...), fp64 in list order: the bits of one LaunchTraverse per tree. DART
+// drops and restores its trees this way. grid_cap > 0 caps the grid (tests: several tiles per
+// block at small row counts).
+void LaunchTraverseForest(const uint32_t* rowbins, int stride_dw, int width, int n, const ForestDev& f, double* score,
+                          int num_cu, int grid_cap, hipStream_t s);
+
 // Score update from the final leaf ranges of the frontier tree just grown (reference
 // serial_tree_learner.cpp AddPredictionToScore via data_partition_, CUDA twin
 // cuda_data_partition.cu AddPredictionToScoreKernel), when every row sits in exactly one

@@ -43,6 +43,24 @@ __device__ __forceinline__ bool CatLeft(const TCat& c, const uint32_t* bits, uin
   return static_cast<int>(w) < c.nwords && ((bits[c.begin + w] >> (b & 31u)) & 1u);
 }
 
+// One level of a walk: the child of node `node` (its packed form `nd`) that a row whose group bin
+// is `gb` goes to (>= 0: a node, < 0: ~leaf). The group-bin predicate of traverse_kernels.h, the
+// one copy every traversal kernel here calls.
+__device__ __forceinline__ int NodeStep(const TNode& nd, uint32_t gb, const TCat* __restrict__ cats,
+                                        const uint32_t* __restrict__ cat_bits, int node) {
+  bool left;
+  if (nd.flags & kTCat) {
+    left = CatLeft(cats[node], cat_bits, gb);
+  } else if (gb < nd.lo || gb > nd.hi) {
+    left = (nd.flags & kTOutLeft) != 0;
+  } else if (static_cast<int>(gb) == nd.gmiss) {
+    left = (nd.flags & kTDefaultLeft) != 0;
+  } else {
+    left = gb <= nd.tg;
+  }
+  return left ? nd.left : nd.right;
+}
+
 // a linear leaf's value for row `row` (reference linear tree Predict: the leaf's constant output
 // when any of the model's features is NaN)
 __device__ __forceinline__ double LinearValue(const LinearLeaves& lin, int leaf, long long row, double leaf_out) {
@@ -115,17 +133,7 @@ __global__ __launch_bounds__(kTThreads) void k_traverse(const uint32_t* __restri
         if (node[j] < 0) continue;
         const TNode nd = s_nodes[node[j]];
         const uint32_t gb = GroupBin<W>(row[j], nd.group);
-        bool left;
-        if (nd.flags & kTCat) {
-          left = CatLeft(cats[node[j]], cat_bits, gb);
-        } else if (gb < nd.lo || gb > nd.hi) {
-          left = (nd.flags & kTOutLeft) != 0;
-        } else if (static_cast<int>(gb) == nd.gmiss) {
-          left = (nd.flags & kTDefaultLeft) != 0;
-        } else {
-          left = gb <= nd.tg;
-        }
-        node[j] = left ? nd.left : nd.right;
+        node[j] = NodeStep(nd, gb, cats, cat_bits, node[j]);
         live |= node[j] >= 0;
       }
     }
@@ -136,6 +144,124 @@ __global__ __launch_bounds__(kTThreads) void k_traverse(const uint32_t* __restri
         const double lv = LIN ? LinearValue(lin, ~node[j], base + r, s_leaf[~node[j]]) : s_leaf[~node[j]];
         score[base + r] = sc[j] + lv;
       }
+    }
+  }
+}
+
+// One tree of a forest over this lane's kTRowsPerThread rows: k_traverse's interleaved walk, then
+// sc[j] += the row's leaf value. nodes / leaf point into LDS (a staged run) or global memory (a
+// tree larger than the run budget); each call site is inlined with its own address space.
+template <int W>
+__device__ __forceinline__ void ForestWalk(const TNode* nodes, int num_nodes, const double* leaf,
+                                           const TCat* __restrict__ cats, const uint32_t* __restrict__ cat_bits,
+                                           const uint8_t* const (&row)[kTRowsPerThread],
+                                           const bool (&valid)[kTRowsPerThread], double (&sc)[kTRowsPerThread]) {
+  // a one-leaf tree of value zero adds nothing (Tree::AddPredictionToScore skips it too)
+  if (num_nodes == 0 && leaf[0] == 0.0) return;
+  int node[kTRowsPerThread];
+#pragma unroll
+  for (int j = 0; j < kTRowsPerThread; ++j) node[j] = valid[j] && num_nodes > 0 ? 0 : ~0;
+  bool live = num_nodes > 0;
+  while (live) {
+    live = false;
+#pragma unroll
+    for (int j = 0; j < kTRowsPerThread; ++j) {
+      if (node[j] < 0) continue;
+      const TNode nd = nodes[node[j]];
+      const uint32_t gb = GroupBin<W>(row[j], nd.group);
+      node[j] = NodeStep(nd, gb, cats, cat_bits, node[j]);
+      live |= node[j] >= 0;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kTRowsPerThread; ++j) {
+    if (valid[j]) sc[j] += leaf[~node[j]];
+  }
+}
+
+// Forest traversal: score[i] = (((score[i] + T_0(i)) + T_1(i)) + ...) over the trees of a packed
+// forest (traverse_pack.h), in list order, one fp64 accumulator per row in a register: the bits
+// of one k_traverse launch per tree, with the rows staged and the score read and written once.
+// No atomics: a row belongs to one lane.
+//
+// A block holds a kTRows-row tile in LDS (as k_traverse: 16-byte loads, rows of at most kTMaxDw
+// dwords; wider rows are read from global memory) and loops over the forest's RUNS with the
+// tile in place: a run's trees (nodes and leaf values, one contiguous range) are copied into
+// LDS, then every lane walks its two rows through the run's trees one after the other. A
+// forest of one run is staged once per block, not once per tile. A tree larger than the budget
+// is a run of its own, walked from global memory; a one-leaf tree adds its value (nothing when
+// that is zero, as Tree::AddPredictionToScore). Categorical nodes read cats / cat_bits from
+// global memory.
+//
+// Run budget kForestRunBytes = 20 KiB. The CU has 160 KiB of LDS and the kernel is bound by the
+// latency of dependent LDS reads (node, then the row's bin, per level), so it wants several waves
+// per SIMD: three blocks of 256 lanes per CU give 3 waves per SIMD and leave 160 / 3 = 53.3 KiB
+// per block. Beside the widest staged row tile (512 rows x 16 dwords = 32 KiB) that is 21.3 KiB;
+// 20 KiB keeps the block at 52 KiB, under the 64 KiB a launch gets without opting in to more.
+// 20 KiB hold 13 trees of 63 leaves (1,504 bytes each) or 58 of 15 leaves; Higgs-width rows
+// (7 dwords, a 14 KiB tile) then run four blocks per CU. A larger budget would save a barrier
+// pair per 13 trees and tile, which the walks of 13 trees dwarf, and cost a block of occupancy.
+template <int W>
+__global__ __launch_bounds__(kTThreads) void k_traverse_forest(const uint32_t* __restrict__ rowbins, int stride_dw, int n,
+                                                               ForestDev f, double* __restrict__ score) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  unsigned char* s_run = lds;
+  uint32_t* s_rows = reinterpret_cast<uint32_t*>(lds + kForestRunBytes);
+  const int t = threadIdx.x;
+  const bool staged = stride_dw <= kTMaxDw;
+  bool resident = false;  // a one-run forest already sits in s_run
+  for (long long base = static_cast<long long>(blockIdx.x) * kTRows; base < n;
+       base += static_cast<long long>(gridDim.x) * kTRows) {
+    const int rows = static_cast<int>(min(static_cast<long long>(kTRows), n - base));
+    double sc[kTRowsPerThread];
+    bool valid[kTRowsPerThread];
+    const uint8_t* row[kTRowsPerThread];
+#pragma unroll
+    for (int j = 0; j < kTRowsPerThread; ++j) {
+      const int r = t + j * kTThreads;
+      valid[j] = r < rows;
+      sc[j] = valid[j] ? score[base + r] : 0.0;
+      row[j] = staged ? reinterpret_cast<const uint8_t*>(s_rows + static_cast<size_t>(r) * stride_dw)
+                      : reinterpret_cast<const uint8_t*>(rowbins + static_cast<size_t>(base + r) * stride_dw);
+    }
+    __syncthreads();  // the previous tile's walks are done: its rows and run may be overwritten
+    if (staged) {
+      const uint32_t* src = rowbins + base * stride_dw;
+      const int ndw = rows * stride_dw;
+      const int nq = (reinterpret_cast<uintptr_t>(src) & 15u) == 0 ? ndw >> 2 : 0;
+      const uint4* src4 = reinterpret_cast<const uint4*>(src);
+      uint4* dst4 = reinterpret_cast<uint4*>(s_rows);
+      for (int k = t; k < nq; k += kTThreads) dst4[k] = src4[k];
+      for (int k = 4 * nq + t; k < ndw; k += kTThreads) s_rows[k] = src[k];
+    }
+    for (int r = 0; r < f.num_runs; ++r) {
+      const TForestRun run = f.runs[r];
+      const bool in_lds = run.bytes <= static_cast<uint32_t>(kForestRunBytes);
+      if (r > 0) __syncthreads();  // the previous run's walks are done
+      if (in_lds && !resident) {
+        const uint4* src4 = reinterpret_cast<const uint4*>(f.blob + run.begin);
+        uint4* dst4 = reinterpret_cast<uint4*>(s_run);
+        for (int k = t; k < static_cast<int>(run.bytes >> 4); k += kTThreads) dst4[k] = src4[k];
+      }
+      __syncthreads();  // the run (and, before the first, the row tile) is in place
+      for (int q = 0; q < run.count; ++q) {
+        const TForestTree tr = f.trees[run.first + q];
+        const TCat* cats = f.cats + tr.cat;
+        if (in_lds) {
+          const unsigned char* b = s_run + (tr.blob - run.begin);
+          const double* leaf = reinterpret_cast<const double*>(b + sizeof(TNode) * tr.num_nodes);
+          ForestWalk<W>(reinterpret_cast<const TNode*>(b), tr.num_nodes, leaf, cats, f.cat_bits, row, valid, sc);
+        } else {
+          const unsigned char* b = f.blob + tr.blob;
+          const double* leaf = reinterpret_cast<const double*>(b + sizeof(TNode) * tr.num_nodes);
+          ForestWalk<W>(reinterpret_cast<const TNode*>(b), tr.num_nodes, leaf, cats, f.cat_bits, row, valid, sc);
+        }
+      }
+    }
+    resident = f.num_runs == 1;
+#pragma unroll
+    for (int j = 0; j < kTRowsPerThread; ++j) {
+      if (valid[j]) score[base + t + j * kTThreads] = sc[j];
     }
   }
 }
@@ -175,17 +301,7 @@ __global__ __launch_bounds__(kTThreads) void k_traverse_col(const uint8_t* __res
         const TNode nd = s_nodes[node[j]];
         const size_t o = static_cast<size_t>(nd.group) * n + row[j];
         const uint32_t gb = W == 1 ? colbins[o] : reinterpret_cast<const uint16_t*>(colbins)[o];
-        bool left;
-        if (nd.flags & kTCat) {
-          left = CatLeft(cats[node[j]], cat_bits, gb);
-        } else if (gb < nd.lo || gb > nd.hi) {
-          left = (nd.flags & kTOutLeft) != 0;
-        } else if (static_cast<int>(gb) == nd.gmiss) {
-          left = (nd.flags & kTDefaultLeft) != 0;
-        } else {
-          left = gb <= nd.tg;
-        }
-        node[j] = left ? nd.left : nd.right;
+        node[j] = NodeStep(nd, gb, cats, cat_bits, node[j]);
         live |= node[j] >= 0;
       }
     }
@@ -244,17 +360,7 @@ __global__ __launch_bounds__(kTThreads) void k_traverse_list(const uint8_t* __re
 #pragma unroll
       for (int j = 0; j < R; ++j) {
         if (node[j] < 0) continue;
-        bool left;
-        if (nd[j].flags & kTCat) {
-          left = CatLeft(cats[node[j]], cat_bits, gb[j]);
-        } else if (gb[j] < nd[j].lo || gb[j] > nd[j].hi) {
-          left = (nd[j].flags & kTOutLeft) != 0;
-        } else if (static_cast<int>(gb[j]) == nd[j].gmiss) {
-          left = (nd[j].flags & kTDefaultLeft) != 0;
-        } else {
-          left = gb[j] <= nd[j].tg;
-        }
-        node[j] = left ? nd[j].left : nd[j].right;
+        node[j] = NodeStep(nd[j], gb[j], cats, cat_bits, node[j]);
         live |= node[j] >= 0;
       }
     }
@@ -365,6 +471,19 @@ void LaunchTraverse(const uint32_t* rowbins, int stride_dw, int width, int n, co
     k_traverse<2, false><<<grid, kTThreads, lds, s>>>(rowbins, stride_dw, n, t.nodes, t.num_nodes, t.cats, t.cat_bits,
                                                      t.leaf_value, t.num_leaves, score, none);
   }
+  HIP_CHECK(hipGetLastError());
+}
+
+void LaunchTraverseForest(const uint32_t* rowbins, int stride_dw, int width, int n, const ForestDev& f, double* score,
+                          int num_cu, int grid_cap, hipStream_t s) {
+  if (n <= 0 || f.num_trees <= 0) return;
+  if (width < 0 || width > 2) Log::Fatal("LaunchTraverseForest: group-bin width %d", width);
+  const size_t lds = kForestRunBytes + (stride_dw <= kTMaxDw ? sizeof(uint32_t) * kTRows * stride_dw : 0);
+  int grid = TraverseGrid(n, num_cu);
+  if (grid_cap > 0) grid = std::min(grid, grid_cap);
+  if (width == 0) k_traverse_forest<0><<<grid, kTThreads, lds, s>>>(rowbins, stride_dw, n, f, score);
+  else if (width == 1) k_traverse_forest<1><<<grid, kTThreads, lds, s>>>(rowbins, stride_dw, n, f, score);
+  else k_traverse_forest<2><<<grid, kTThreads, lds, s>>>(rowbins, stride_dw, n, f, score);
   HIP_CHECK(hipGetLastError());
 }
 

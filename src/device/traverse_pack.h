@@ -11,6 +11,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include "lgap/dataset.h"
 #include "lgap/log.h"
@@ -121,6 +122,126 @@ inline CompactTreeDev CompactTreeAt(const char* base, const CompactLayout& z, in
   return {reinterpret_cast<const TNode*>(base), reinterpret_cast<const TCat*>(base + z.cat),
           reinterpret_cast<const uint32_t*>(base + z.bit), reinterpret_cast<const double*>(base + z.leaf),
           num_leaves - 1, num_leaves};
+}
+
+// ---- A forest: `count` compact trees in one upload, walked in list order by one pass over the
+// rows (k_traverse_forest). Every tree is one contiguous blob, its nodes then its leaf values
+// (a multiple of 16 bytes), so a RUN of consecutive trees is one contiguous byte range that the
+// kernel copies into LDS with 16-byte loads. A run holds as many consecutive trees as fit
+// kForestRunBytes (the budget's reasoning: the kernel's header comment); a tree larger than
+// the budget is a run of its own whose nodes and leaves are read from global memory. A
+// one-leaf tree has no nodes and one leaf value. Categorical node data is kept only for trees
+// that have a categorical node; TCat::begin already includes the tree's offset into the
+// forest's categorical words.
+constexpr int kForestRunBytes = 20 * 1024;
+
+struct TForestTree {
+  uint32_t blob;  // byte offset of the tree's nodes in the blob part; its leaf values follow them
+  int32_t cat;    // index of node 0's TCat (meaningful for trees with a categorical node)
+  int32_t num_nodes, num_leaves;
+};
+static_assert(sizeof(TForestTree) == 16, "TForestTree layout");
+struct TForestRun {
+  int32_t first, count;  // trees [first, first + count)
+  uint32_t begin, bytes;  // their blobs; bytes > kForestRunBytes: one tree, walked from global memory
+};
+
+inline size_t ForestTreeBytes(int num_leaves) {
+  return sizeof(TNode) * static_cast<size_t>(num_leaves - 1) + ((sizeof(double) * num_leaves + 15) & ~static_cast<size_t>(15));
+}
+
+inline bool HasCategoricalNode(const Tree* tree) {
+  for (int i = 0; i < tree->num_leaves() - 1; ++i) {
+    if (Tree::GetDecisionType(tree->decision_type(i), kCategoricalMask)) return true;
+  }
+  return false;
+}
+
+// offsets of the run table, the blobs, the categorical node data and the categorical words
+// (the tree table sits at 0)
+struct ForestLayout {
+  size_t run, blob, cat, bit, total;
+  int num_trees;
+  std::vector<TForestRun> runs;
+};
+inline ForestLayout CompactForestLayout(const Tree* const* trees, int count) {
+  ForestLayout z;
+  z.num_trees = count;
+  size_t blob = 0, cats = 0, bits = 0;
+  for (int i = 0; i < count; ++i) {
+    const size_t b = ForestTreeBytes(trees[i]->num_leaves());
+    if (z.runs.empty() || z.runs.back().bytes + b > static_cast<size_t>(kForestRunBytes)) {
+      z.runs.push_back({i, 0, static_cast<uint32_t>(blob), 0u});
+    }
+    z.runs.back().count += 1;
+    z.runs.back().bytes += static_cast<uint32_t>(b);
+    blob += b;
+    if (HasCategoricalNode(trees[i])) {
+      cats += trees[i]->num_leaves() - 1;
+      bits += trees[i]->cat_threshold_inner().size();
+    }
+  }
+  z.run = Round256(sizeof(TForestTree) * std::max(count, 1));
+  z.blob = z.run + Round256(sizeof(TForestRun) * std::max<size_t>(z.runs.size(), 1));
+  z.cat = z.blob + Round256(std::max<size_t>(blob, 16));
+  z.bit = z.cat + Round256(sizeof(TCat) * std::max<size_t>(cats, 1));
+  z.total = z.bit + sizeof(uint32_t) * std::max<size_t>(bits, 1);
+  return z;
+}
+
+// `trees` (each at most 32768 leaves) into the z.total bytes at hp. The leaf values are copied
+// as they are now: the caller may rescale the trees afterwards.
+inline void PackCompactForest(const Tree* const* trees, const Dataset* data, char* hp, const ForestLayout& z) {
+  TForestTree* tt = reinterpret_cast<TForestTree*>(hp);
+  std::memcpy(hp + z.run, z.runs.data(), sizeof(TForestRun) * z.runs.size());
+  TCat* cats = reinterpret_cast<TCat*>(hp + z.cat);
+  uint32_t* cw = reinterpret_cast<uint32_t*>(hp + z.bit);
+  size_t blob = 0;
+  int cat_at = 0, bit_at = 0;
+  for (int i = 0; i < z.num_trees; ++i) {
+    const Tree* tree = trees[i];
+    const int nn = tree->num_leaves() - 1, nl = tree->num_leaves();
+    LGAP_CHECK(nn <= 32767);  // (children are int16_t)
+    const bool has_cat = HasCategoricalNode(tree);
+    tt[i] = {static_cast<uint32_t>(blob), has_cat ? cat_at : 0, nn, nl};
+    TNode* nodes = reinterpret_cast<TNode*>(hp + z.blob + blob);
+    const auto& cb = tree->cat_boundaries_inner();
+    for (int n = 0; n < nn; ++n) {
+      const int8_t dt = tree->decision_type(n);
+      const int thr = static_cast<int>(tree->threshold_in_bin(n));
+      const bool cat = Tree::GetDecisionType(dt, kCategoricalMask);
+      TCat unused;
+      PackCompactNode(data->feature(tree->split_feature_inner(n)), dt, thr, tree->left_child(n), tree->right_child(n),
+                      cat ? bit_at + cb[thr] : 0, cat ? cb[thr + 1] - cb[thr] : 0, &nodes[n],
+                      has_cat ? &cats[cat_at + n] : &unused);
+    }
+    double* lv = reinterpret_cast<double*>(hp + z.blob + blob + sizeof(TNode) * nn);
+    for (int l = 0; l < nl; ++l) lv[l] = tree->LeafOutput(l);
+    if (nl & 1) lv[nl] = 0.0;  // (the blob's padding)
+    if (has_cat) {
+      const auto& ct = tree->cat_threshold_inner();
+      for (size_t w = 0; w < ct.size(); ++w) cw[bit_at + w] = ct[w];
+      cat_at += nn;
+      bit_at += static_cast<int>(ct.size());
+    }
+    blob += ForestTreeBytes(nl);
+  }
+}
+
+// the packed forest as LaunchTraverseForest takes it
+struct ForestDev {
+  const TForestTree* trees;
+  const TForestRun* runs;
+  const unsigned char* blob;
+  const TCat* cats;
+  const uint32_t* cat_bits;
+  int num_trees, num_runs;
+};
+// base: the device copy of what PackCompactForest wrote
+inline ForestDev CompactForestAt(const char* base, const ForestLayout& z) {
+  return {reinterpret_cast<const TForestTree*>(base), reinterpret_cast<const TForestRun*>(base + z.run),
+          reinterpret_cast<const unsigned char*>(base + z.blob), reinterpret_cast<const TCat*>(base + z.cat),
+          reinterpret_cast<const uint32_t*>(base + z.bit), z.num_trees, static_cast<int>(z.runs.size())};
 }
 
 }  // namespace device

@@ -6,6 +6,9 @@
 // visible: no silent CPU fallback.
 #include "lgap/tree_learner.h"
 
+#include <cstdlib>
+#include <cstring>
+
 #include "device/engine_plan.h"
 #include "lgap/device_api.h"
 #include "lgap/log.h"
@@ -27,6 +30,18 @@ std::unique_ptr<TreeLearner> CreateHost(const std::string& learner_type, bool li
 }
 
 }  // namespace
+
+DeviceDart DeviceDartMode() {
+  static const DeviceDart mode = [] {
+    const char* e = std::getenv("LGAP_DEVICE_DART");
+    if (e == nullptr || std::strcmp(e, "tree") == 0) return DeviceDart::kTree;
+    if (std::strcmp(e, "forest") == 0) return DeviceDart::kForest;
+    if (std::strcmp(e, "0") == 0) return DeviceDart::kHost;
+    Log::Fatal("LGAP_DEVICE_DART: unknown value '%s' (forest, tree or 0)", e);
+    return DeviceDart::kTree;
+  }();
+  return mode;
+}
 
 // Only a learner that owns the score on the device serves these (the boosting loop refuses
 // earlier, with the advice to use Booster.update; reaching them is a routing bug).
