@@ -145,6 +145,13 @@ class GBDT {
       *h = hessians_;
     }
   }
+  // Learned position biases of unbiased LTR by position id: the device learner's when its kernels
+  // compute the gradients, else the host objective's (empty: no positions).
+  void GetPositionBiases(std::vector<double>* out) const {
+    out->clear();
+    if (device_mode_ && learner_ && learner_->DeviceGetPositionBiases(out)) return;
+    if (objective_ == nullptr || !objective_->GetPositionBiases(out)) out->clear();
+  }
   const Config* config() const { return config_; }
   int best_iteration() const { return best_iter_; }
   std::string parser_config_str_;

@@ -330,6 +330,9 @@ LIGHTGBM_C_EXPORT int LGBM_DeviceSynchronize();
 // ---- kernel-level entry points (numerics tests / ops module)
 // Gradients and hessians of the last boosting round (class-major); pass null buffers to query *out_len.
 LIGHTGBM_C_EXPORT int LGBM_BoosterGetGradients(BoosterHandle handle, int64_t* out_len, float* grad, float* hess);
+// Learned position biases of a lambdarank booster trained with positions, by position id (read-only; 0 without
+// positions); pass a null buffer to query *out_len.
+LIGHTGBM_C_EXPORT int LGBM_BoosterGetPositionBiases(BoosterHandle handle, int64_t* out_len, double* out);
 // Packed group layout: groups, total histogram bins, bytes per group bin, per-group histogram start.
 LIGHTGBM_C_EXPORT int LGBM_DatasetGetGroupLayout(DatasetHandle handle, int* num_groups, int* num_total_bin,
                                                  int* bin_width, int32_t* hist_start);

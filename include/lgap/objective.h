@@ -45,6 +45,8 @@ class ObjectiveFunction {
   virtual void ConvertOutput(const double* input, double* output) const { output[0] = input[0]; }
   virtual data_size_t NumPositiveData() const { return 0; }
   virtual bool IsRanking() const { return false; }
+  // unbiased LTR: the learned position biases by position id (false: the objective keeps none)
+  virtual bool GetPositionBiases(std::vector<double>* /*out*/) const { return false; }
   virtual DeviceGradKind device_kind() const { return DeviceGradKind::kHostOnly; }
   // pointwise objectives: formula parameters, (possibly transformed) labels, MAPE label weights
   virtual const PointwiseParams* pointwise() const { return nullptr; }

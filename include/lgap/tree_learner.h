@@ -103,6 +103,8 @@ class TreeLearner {
   virtual void DeviceAddConstant(double, int class_id) { (void)class_id; }
   virtual void DeviceGetScore(std::vector<double>*) const {}
   virtual void DeviceGetGradients(std::vector<score_t>*, std::vector<score_t>*) const {}
+  // unbiased LTR: the position biases the device gradient kernels learned (false: the learner holds none)
+  virtual bool DeviceGetPositionBiases(std::vector<double>*) const { return false; }
   // Row sampling drawn on the device from the device-resident gradients.
   // L1 / quantile / MAPE leaf renewal from the device-resident score and partition
   // (false: not handled, the host renews from a downloaded score)

@@ -94,6 +94,19 @@ def booster_gradients(booster: Booster) -> Tuple[np.ndarray, np.ndarray]:
     return g, h
 
 
+def position_biases(booster: Booster) -> np.ndarray:
+    """Learned position biases of a lambdarank booster trained with positions (unbiased LTR), by position
+    id, as float64: the device learner's when it computes the gradients, else the host objective's (held as
+    float32 there). Empty without positions. Read-only."""
+    n = ctypes.c_int64(0)
+    _check(_LIB.LGBM_BoosterGetPositionBiases(booster.handle, ctypes.byref(n), None))
+    out = np.zeros(n.value, dtype=np.float64)
+    if n.value:
+        _check(_LIB.LGBM_BoosterGetPositionBiases(booster.handle, ctypes.byref(n),
+                                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+    return out
+
+
 def _param_str(params: Optional[dict]) -> bytes:
     return " ".join(f"{k}={v}" for k, v in (params or {}).items()).encode()
 

@@ -1417,6 +1417,15 @@ int LGBM_BoosterGetGradients(BoosterHandle handle, int64_t* out_len, float* grad
   API_END();
 }
 
+int LGBM_BoosterGetPositionBiases(BoosterHandle handle, int64_t* out_len, double* out) {
+  API_BEGIN();
+  std::vector<double> b;
+  B(handle)->boosting_->GetPositionBiases(&b);
+  *out_len = static_cast<int64_t>(b.size());
+  if (out) std::copy(b.begin(), b.end(), out);
+  API_END();
+}
+
 int LGBM_DatasetGetGroupLayout(DatasetHandle handle, int* num_groups, int* num_total_bin, int* bin_width,
                                int32_t* hist_start) {
   API_BEGIN();

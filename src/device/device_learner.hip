@@ -798,6 +798,14 @@ class DeviceTreeLearner : public TreeLearner {
     }
   }
 
+  bool DeviceGetPositionBiases(std::vector<double>* out) const override {
+    if (rank_args_.positions == nullptr || pos_bias_.size() == 0) return false;
+    out->resize(pos_bias_.size());
+    HIP_CHECK(hipMemcpyAsync(out->data(), pos_bias_.get(), out->size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    return true;
+  }
+
   // `p` is memory of this learner's device (hipMalloc'd by anyone in the process, torch included)
   void RequireTrainingDeviceMemory(const void* p, const char* who, const char* what) const {
     hipPointerAttribute_t attr{};

@@ -108,6 +108,10 @@ class RankingBase : public ObjectiveFunction {
   bool NeedAccuratePrediction() const override { return false; }
   bool IsRanking() const override { return true; }
   const std::vector<label_t>& position_biases() const { return pos_biases_; }
+  bool GetPositionBiases(std::vector<double>* out) const override {
+    out->assign(pos_biases_.begin(), pos_biases_.end());
+    return true;
+  }
   double position_learning_rate() const { return learning_rate_; }
   double position_regularization() const { return pos_reg_; }
   const std::vector<double>& effective_pairs() const { return effective_pairs_; }

@@ -346,38 +346,8 @@ def test_device_goss_selection(lgb, gpu_required, rng, num_class):
             np.testing.assert_array_equal(gk2[~sampled], gk[~sampled])
 
 
-def _torch_xendcg(score, label, sizes, seed, weight=None):
-    """rank_xendcg lambdas / hessians (rank_objective.hpp RankXENDCG::GetGradientsForOneQuery) in
-    PyTorch fp64, with each query's Random(seed + q) NextFloat draws reproduced."""
-    import torch
-
-    g = torch.zeros(len(score), dtype=torch.float64)
-    h = torch.zeros(len(score), dtype=torch.float64)
-    start = 0
-    for q, cnt in enumerate(sizes):
-        cnt = int(cnt)
-        if cnt > 1:
-            s = torch.as_tensor(score[start:start + cnt], dtype=torch.float64)
-            rho = torch.softmax(s, 0)
-            x = (seed + q) & 0xFFFFFFFF
-            draws = []
-            for _ in range(cnt):
-                x = (214013 * x + 2531011) & 0xFFFFFFFF
-                draws.append(float(np.float32((x >> 16) & 0x7FFF) / np.float32(32768.0)))
-            params = torch.pow(2.0, torch.as_tensor(label[start:start + cnt]).to(torch.int64).double()) \
-                - torch.as_tensor(draws, dtype=torch.float64)
-            inv_den = 1.0 / max(1e-15, float(params.sum()))
-            t1 = -params * inv_den + rho
-            p1 = t1 / (1 - rho)
-            t2 = rho * (p1.sum() - p1)
-            p2 = t2 / (1 - rho)
-            t3 = rho * (p2.sum() - p2)
-            g[start:start + cnt] = t1 + t2 + t3
-            h[start:start + cnt] = rho * (1 - rho)
-        start += cnt
-    if weight is not None:
-        g, h = g * torch.as_tensor(weight, dtype=torch.float64), h * torch.as_tensor(weight, dtype=torch.float64)
-    return g.numpy(), h.numpy()
+# the float64 reference of rank_xendcg: now numpy, shared with test_rank_kernels.py
+from rank_cases import xendcg_reference as _torch_xendcg  # noqa: E402
 
 
 @pytest.mark.parametrize("weighted", [False, True])
