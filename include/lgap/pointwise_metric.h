@@ -37,6 +37,16 @@ LGAP_HD inline double PmConvert(const PwMetricParams& p, double s) {
   }
 }
 
+// The clamp of the log losses is the reference's kEpsilon, a float there (meta.h: `const score_t
+// kEpsilon = 1e-15f`). In `p > kEpsilon` it is promoted: the threshold is 1.0000000036e-15. In
+// `return -std::log(kEpsilon)` the argument is a float, so the float overload is taken and the clamped
+// loss is the float -logf(1e-15f) = 34.5387764 widened to double, 34.538776397705078: neither the
+// double log of the promoted float (34.53877639128) nor that of a double 1e-15 (34.53877639491). It is
+// written out, so that the host's and the device's logf cannot differ in it; the true value lies
+// 6.4e-9 from this float and the neighbouring floats 3.8e-6 away.
+constexpr double kMetricEpsilon = 1e-15f;
+constexpr double kMetricClampLoss = 34.538776397705078;
+
 LGAP_HD inline double PmSafeLog(double x) { return x > 0 ? log(x) : -INFINITY; }
 
 LGAP_HD inline double PmXent(double y, double p) {
@@ -90,11 +100,11 @@ LGAP_HD inline double PmLoss(const PwMetricParams& p, double y, double s, double
     }
     case kPmBinLogloss:
       if (y <= 0) {
-        if (1.0f - s > kEpsilon) return -log(1.0f - s);
-      } else if (s > kEpsilon) {
+        if (1.0f - s > kMetricEpsilon) return -log(1.0f - s);
+      } else if (s > kMetricEpsilon) {
         return -log(s);
       }
-      return -log(kEpsilon);
+      return kMetricClampLoss;
     case kPmBinError:
       return s <= 0.5f ? (y > 0) : (y <= 0);
     case kPmXent:
@@ -149,7 +159,7 @@ LGAP_HD inline double MultiRowLoss(const MultiMetricParams& p, const double* s, 
     }
     return 0.0;
   }
-  return py > kEpsilon ? -log(py) : -log(kEpsilon);
+  return py > kMetricEpsilon ? -log(py) : kMetricClampLoss;
 }
 
 }  // namespace lgap

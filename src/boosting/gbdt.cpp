@@ -464,13 +464,13 @@ std::vector<double> GBDT::EvalTraining(const Metric* m, const double** score) {
 // host copy, refreshed once when stale.
 std::vector<double> GBDT::EvalValid(size_t d, const Metric* m) {
   PwMetricParams p;
-  if (valid_dev_[d] >= 0 && num_tree_per_iteration_ == 1 && m->DevicePointwise(objective_, &p)) {
+  const char* off = std::getenv("LGAP_DEVICE_METRICS");  // "0": the host for every metric, as in EvalTraining
+  const bool allow = off == nullptr || std::strcmp(off, "0") != 0;
+  if (allow && valid_dev_[d] >= 0 && num_tree_per_iteration_ == 1 && m->DevicePointwise(objective_, &p)) {
     double sum = 0.0;
     if (learner_->DeviceEvalPointwise(valid_dev_[d], p, 0, &sum)) return m->FinishSum(sum);
   }
   RankMetricSpec rs;
-  const char* off = std::getenv("LGAP_DEVICE_METRICS");
-  const bool allow = off == nullptr || std::strcmp(off, "0") != 0;
   if (allow && valid_dev_[d] >= 0 && num_tree_per_iteration_ == 1 && m->DeviceRankSpec(&rs)) {
     std::vector<double> raw;
     if (learner_->DeviceEvalRank(valid_dev_[d], rs, 0, &raw)) return m->FinishRank(raw);

@@ -64,7 +64,7 @@ bool MetricEval::AucMu(const ScoreView& v, const AucMuSpec& spec, std::vector<do
     slot->lab.Resize(std::max(maxpair, 1));
     slot->w.Resize(std::max(maxpair, 1));
     slot->scratch.Resize(AucScratchBytes(std::max(maxpair, 1)));
-    slot->out.Resize(2 * static_cast<size_t>(npairs));
+    slot->out.Resize(kAucOutWords * static_cast<size_t>(npairs));
   }
   AucMuState& st = *slot;
   AucMuPairArgs pa;
@@ -89,16 +89,16 @@ bool MetricEval::AucMu(const ScoreView& v, const AucMuSpec& spec, std::vector<do
       pa.nj = (*spec.sizes)[j];
       LaunchAucMuPair(pa, s);
       LaunchAucMetric(false, st.dist.get(), st.lab.get(), v.weight != nullptr ? st.w.get() : nullptr, pa.ni + pa.nj,
-                      st.scratch.get(), st.scratch.size(), st.out.get() + 2 * q, s);
+                      st.scratch.get(), st.scratch.size(), st.out.get() + kAucOutWords * q, s);
       jstart += (*spec.sizes)[j];
     }
     istart += (*spec.sizes)[i];
   }
-  std::vector<double> h(2 * static_cast<size_t>(npairs));
+  std::vector<double> h(kAucOutWords * static_cast<size_t>(npairs));
   st.out.Download(h.data(), h.size(), s);
   HIP_CHECK(hipStreamSynchronize(s));
   out->assign(npairs, 0.0);
-  for (int p = 0; p < npairs; ++p) (*out)[p] = h[2 * p];
+  for (int p = 0; p < npairs; ++p) (*out)[p] = h[kAucOutWords * p];
   return true;
 }
 
@@ -156,7 +156,7 @@ bool MetricEval::Rank(const ScoreView& v, const RankMetricSpec& spec, int k, std
     slot = std::move(fresh);
   }
   RankEvalState& r = *slot;
-  int nout = 2;
+  int nout = kAucOutWords;
   if (query) {
     QueryMetricArgs qa;
     qa.kind = spec.kind;

@@ -19,7 +19,9 @@ namespace device {
 
 // Scratch of an AUC / average-precision evaluation over n rows.
 size_t AucScratchBytes(int n);
-// out (device, 2 doubles) = {accumulator, positive weight}; the host finishes the value.
+// out (device, kAucOutWords doubles) = {accumulator, positive weight, negative weight}; the host
+// finishes the value (a total of exactly zero: that class has no weighted row).
+constexpr int kAucOutWords = 3;
 void LaunchAucMetric(bool average_precision, const double* score, const float* label, const float* weight, int n,
                      void* scratch, size_t scratch_bytes, double* out, hipStream_t s);
 

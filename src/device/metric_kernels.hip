@@ -31,7 +31,10 @@ struct ToPN {
   __host__ __device__ PN operator()(const float2& v) const { return PN{static_cast<double>(v.x), static_cast<double>(v.y)}; }
 };
 
-// -0.0 and +0.0 compare equal but are distinct radix keys: one canonical zero
+// -0.0 and +0.0 compare equal but are distinct radix keys: one canonical zero. The segmented sort
+// of k_rank_keys needs it (a stable tie order among zeros). In k_auc_prep it is defence only: the
+// descending sort leaves +0.0 and -0.0 adjacent and reduce-by-key's equal_to<double> merges them
+// without it, so no test can tell its absence there.
 __device__ __forceinline__ double CanonKey(double s) { return s == 0.0 ? 0.0 : s; }
 
 // block sum over 4 waves in a fixed order (the same value in every thread)
@@ -89,6 +92,7 @@ __global__ __launch_bounds__(kMThreads) void k_auc_fold(const double* __restrict
     const int U = *count;
     out[0] = s;
     out[1] = U > 0 ? pref[U - 1].p + agg[U - 1].p : 0.0;
+    out[2] = U > 0 ? pref[U - 1].n + agg[U - 1].n : 0.0;  // zero iff no negative row has weight
   }
 }
 
@@ -230,7 +234,7 @@ void LaunchAucMetric(bool average_precision, const double* score, const float* l
   p += Align256(sizeof(int));
   double* partial = reinterpret_cast<double*>(p);
   if (n <= 0) {
-    HIP_CHECK(hipMemsetAsync(out, 0, 2 * sizeof(double), s));
+    HIP_CHECK(hipMemsetAsync(out, 0, kAucOutWords * sizeof(double), s));
     return;
   }
   k_auc_prep<<<StreamGrid(n), kMThreads, 0, s>>>(score, label, weight, n, k0, v0);

@@ -243,15 +243,19 @@ class AUCMetric : public Metric {
     out->weights = w_;
     return true;
   }
-  // device sums {accumulator, positive weight} -> the value, as the end of Eval below
+  // One class only: the positive or the negative total is exactly zero. A sum of non-negative
+  // weights is zero in any order iff all are, while the reference's `sum_pos != sumw_` compares two
+  // sums taken in different orders, which need not agree to the last bit on a set of positives only.
+  // With both classes present the reference's own `sum_pos != sumw_` stays, on purpose: no value
+  // changes on a two-class set. That clause is still order-dependent: where the negatives are tiny
+  // next to the positives the two sums can agree by rounding, and the value is then 1.0 as in the
+  // reference, in place of a division by sumw_ - sum_pos == 0.
+  bool TwoClasses(double sum_pos, double sum_neg) const { return sum_pos > 0.0 && sum_neg > 0.0 && sum_pos != sumw_; }
+  // device sums {accumulator, positive weight, negative weight} -> the value, as the end of Eval below
   std::vector<double> FinishRank(const std::vector<double>& v) const override {
-    const double accum = v[0], sum_pos = v[1];
+    const double accum = v[0], sum_pos = v[1], sum_neg = v[2];
     double r = 1.0;
-    if (ap_) {
-      if (sum_pos > 0.0 && sum_pos != sumw_) r = accum / sum_pos;
-    } else if (sum_pos > 0.0 && sum_pos != sumw_) {
-      r = accum / (sum_pos * (sumw_ - sum_pos));
-    }
+    if (TwoClasses(sum_pos, sum_neg)) r = ap_ ? accum / sum_pos : accum / (sum_pos * (sumw_ - sum_pos));
     return {r};
   }
   std::vector<double> Eval(const double* score, const ObjectiveFunction*) const override {
@@ -261,7 +265,7 @@ class AUCMetric : public Metric {
     // tied scores form one group below, so their order is free: an unstable parallel sort
     // (reference binary_metric.hpp:200 Common::ParallelSort)
     common::ParallelSort(&idx, [score](data_size_t a, data_size_t b) { return score[a] > score[b]; });
-    double cur_pos = 0, sum_pos = 0, accum = 0, cur_neg = 0;
+    double cur_pos = 0, sum_pos = 0, accum = 0, cur_neg = 0, sum_neg = 0;
     double sum_pred_pos = 0, accum_prec = 1.0;
     double thr = score[idx[0]];
     for (data_size_t i = 0; i < n_; ++i) {
@@ -279,24 +283,26 @@ class AUCMetric : public Metric {
           accum += cur_neg * (cur_pos * 0.5f + sum_pos);
           sum_pos += cur_pos;
         }
+        sum_neg += cur_neg;
         cur_neg = cur_pos = 0.0;
       }
       cur_neg += (y <= 0) * w;
       cur_pos += (y > 0) * w;
     }
+    sum_neg += cur_neg;
     if (ap_) {
       sum_pos += cur_pos;
       sum_pred_pos += cur_pos + cur_neg;
       accum_prec = sum_pos / sum_pred_pos;
       accum += cur_pos * accum_prec;
       double v = 1.0;
-      if (sum_pos > 0.0 && sum_pos != sumw_) v = accum / sum_pos;
+      if (TwoClasses(sum_pos, sum_neg)) v = accum / sum_pos;
       return {v};
     }
     accum += cur_neg * (cur_pos * 0.5f + sum_pos);
     sum_pos += cur_pos;
     double auc = 1.0;
-    if (sum_pos > 0.0 && sum_pos != sumw_) auc = accum / (sum_pos * (sumw_ - sum_pos));
+    if (TwoClasses(sum_pos, sum_neg)) auc = accum / (sum_pos * (sumw_ - sum_pos));
     return {auc};
   }
 
@@ -348,7 +354,7 @@ class MulticlassMetric : public Metric {
           }
         }
       } else {
-        l = rec[y] > kEpsilon ? -std::log(rec[y]) : -std::log(kEpsilon);
+        l = rec[y] > kMetricEpsilon ? -std::log(rec[y]) : kMetricClampLoss;
       }
       sum += w_ ? l * w_[i] : l;
     }
