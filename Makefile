@@ -40,6 +40,9 @@ $(BUILD)/%.hip.o: src/%.hip $(HEADERS)
 $(BUILD)/device/predict_kernels.hip.o: HIPFLAGS += -ffp-contract=off
 # the same for predict_contrib_device's weights and sums (contrib_pack.h)
 $(BUILD)/device/contrib_kernels.hip.o: HIPFLAGS += -ffp-contract=off
+# the blended score updates of boosting=rf, (s * a + v) * b in the host's three roundings
+# (blend_kernels.h): contracted, the multiply and the add become one fused multiply-add
+$(BUILD)/device/blend_kernels.hip.o: HIPFLAGS += -ffp-contract=off
 
 $(LIB): $(CPP_OBJS) $(HIP_OBJS)
 	@mkdir -p $(OUT)

@@ -94,7 +94,7 @@ class GBDT {
   // into device memory of the caller (out_dev == nullptr: only *out_len and *out_device).
   void GetRawScoreDevice(int data_idx, int64_t* out_len, int* out_device, double* out_dev);
   void RefitTree(const std::vector<std::vector<int>>& leaf_preds);
-  void MergeFrom(const GBDT* other);
+  virtual void MergeFrom(const GBDT* other);
   void ShuffleModels(int start_iter, int end_iter);
 
   // prediction on raw feature rows
@@ -246,9 +246,17 @@ class RF : public GBDT {
             const std::vector<const Metric*>& training_metrics) override;
   bool TrainOneIter(const score_t* gradients, const score_t* hessians) override;
   void RollbackOneIter() override;
+  void MergeFrom(const GBDT* other) override;
   bool NeedAccuratePrediction() const override { return true; }  // rf.hpp:224: no early stopping
 
  private:
+  // device mode (a learner that owns the score, RF::Init): the running average on the device
+  bool TrainOneIterOnDevice();
+  void BlendIntoScores(const Tree* tree, int k, const ScoreBlend& b);
+  void PrepareDeviceGradients();
+  void LeaveDeviceMode(const char* why);
+  bool grads_kept_ = false;   // the learner holds a copy of the gradients (quantized training)
+  bool grads_dirty_ = false;  // the device gradients were de-quantized in place
   std::vector<double> init_scores_;
   std::vector<score_t> tmp_grad_, tmp_hess_;
 };

@@ -388,6 +388,13 @@ LIGHTGBM_C_EXPORT int LGBM_DeviceTestLinearGram(const float* raw, int32_t num_da
 LIGHTGBM_C_EXPORT int LGBM_DeviceTestForestScore(DatasetHandle handle, BoosterHandle booster, const int32_t* tree_idx,
                                                  const double* scales, int num_trees, const double* score, int grid,
                                                  int per_tree, double* out, int32_t* out_info);
+// Direct test of the blended score update (boosting=rf's running average) over the packed rows of a
+// constructed Dataset: tree tree_idx of booster is blended into a copy of score [num_data], out[i] =
+// divide ? (score[i] * pre + tree(i)) / post : (score[i] * pre + tree(i)) * post, three fp64
+// roundings. grid > 0 caps the kernel's grid.
+LIGHTGBM_C_EXPORT int LGBM_DeviceTestBlendScore(DatasetHandle handle, BoosterHandle booster, int tree_idx,
+                                                const double* score, double pre, double post, int divide, int grid,
+                                                double* out);
 // How that forest is split into LDS runs (no GPU needed): out_run_trees [num_trees] the trees per
 // run, out_run_bytes [num_trees] their bytes, *out_num_runs, and *out_budget the run byte budget.
 LIGHTGBM_C_EXPORT int LGBM_DeviceTestForestRuns(BoosterHandle booster, const int32_t* tree_idx, int num_trees,

@@ -116,6 +116,13 @@ bool TestQuantize(const Dataset* data, const Config& config, bool const_hess, co
 // null): {group-bin width of the rows read (0 = 4-bit rows, 1, 2 bytes), dwords per row}.
 void TestForestScore(const Dataset* data, const Config& config, const Tree* const* trees, const double* scales,
                      int count, const double* score, int grid_cap, bool per_tree, double* out, int* info);
+// Direct test of the blended score update (tests/test_blend_score_kernel.py): a device learner of
+// `config` on `data` with `score` [N] as its one-class training score; `tree` is blended in by the
+// traversal route of DeviceBlendTreeIntoScore (a one-leaf tree: the blended constant): out[i] =
+// divide ? (score[i] * pre + tree(i)) / post : (score[i] * pre + tree(i)) * post. grid_cap > 0 caps
+// the kernel's grid.
+void TestBlendScore(const Dataset* data, const Config& config, const Tree* tree, const double* score, double pre,
+                    double post, bool divide, int grid_cap, double* out);
 // Direct test of the linear-leaf Gram kernels (tests/test_linear_gram_kernel.py), no Dataset:
 // raw[N][F], grad / hess[N]; leaf l reads segs[3 l ..] = (buffer, start, count): buffer 0 the
 // positions [start, start + count) of rows[num_rows], buffer -1 the rows start .. start + count

@@ -36,6 +36,20 @@ struct TreeRef {
   int class_id;
 };
 
+// One edit of a score by a tree's value v at the row, three separately rounded fp64 operations:
+// s = divide ? (s * pre + v) / post : (s * pre + v) * post. boosting=rf averages its trees this
+// way (RF::TrainOneIter: pre = iter, post = 1 / (iter + 1); RF::RollbackOneIter: the negated tree,
+// pre = iter, post = iter - 1 divided by, or post = 1 multiplied by at iter == 1).
+struct ScoreBlend {
+  double pre;
+  double post;
+  bool divide;
+};
+
+// LGAP_DEVICE_RF, read once: unset / "1": boosting=rf keeps its averaged scores on a learner that
+// owns the score; "0": scores, averaging and metrics on the host. Any other value is fatal.
+bool DeviceRfMode();
+
 // LGAP_DEVICE_DART, read once: how boosting=dart trains on a learner that owns the score.
 // unset / "tree": the score stays on the device, one single-tree traversal per dropped tree;
 // "forest": on the device, the dropped trees rescored by one forest traversal per class; "0":
@@ -93,6 +107,14 @@ class TreeLearner {
   virtual int DeviceId() const { return -1; }
   virtual std::unique_ptr<Tree> DeviceTrain(int class_id, bool is_first_tree) { (void)class_id; (void)is_first_tree; return nullptr; }
   virtual void DeviceAddTreeToScore(const Tree*, int class_id) { (void)class_id; }
+  // score = blend(score, tree(row)) instead of score += tree(row) (ScoreBlend), the training
+  // score of class_id or device validation set `id`; a one-leaf tree blends its constant in
+  virtual void DeviceBlendTreeIntoScore(const Tree*, int class_id, const ScoreBlend&) { (void)class_id; }
+  virtual void DeviceBlendTreeIntoValid(int /*id*/, const Tree*, int /*class_id*/, const ScoreBlend&) {}
+  // a copy of the device gradients kept aside, and the gradients restored from it (boosting=rf:
+  // its gradients never change, quantized training de-quantizes them in place)
+  virtual void DeviceKeepGradients(int /*num_class*/) {}
+  virtual void DeviceRestoreGradients(int /*num_class*/) {}
   // Several trees at once (DART's dropped trees): every row adds its class's trees in list
   // order, as `count` DeviceAddTreeToScore / DeviceAddTreeToValid calls would
   virtual void DeviceAddTreesToScore(const TreeRef* /*trees*/, int /*count*/) {}

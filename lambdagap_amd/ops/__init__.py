@@ -15,7 +15,7 @@ from ..basic import _LIB, Booster, Dataset, _check
 
 __all__ = ["group_layout", "group_bins", "device_histogram", "device_sample_rows", "booster_gradients",
            "frontier_histogram", "frontier_partition", "quantize_gradients", "linear_gram", "forest_score",
-           "forest_runs"]
+           "forest_runs", "blend_score"]
 
 
 def group_layout(ds: Dataset) -> Tuple[int, int, int, np.ndarray]:
@@ -308,6 +308,29 @@ def forest_score(ds: Dataset, booster: Booster, trees, scales, score: np.ndarray
     if info is not None:
         info["row_bits"] = (4, 8, 16)[int(fmt[0])]
         info["stride_dw"] = int(fmt[1])
+    return out[:s.size]
+
+
+def blend_score(ds: Dataset, booster: Booster, tree: int, score: np.ndarray, pre: float, post: float,
+                divide: bool = False, grid: Optional[int] = None) -> np.ndarray:
+    """The blended score update (boosting=rf's running average on the GPU) over the packed rows of a
+    constructed Dataset.
+
+    Tree ``tree`` of ``booster`` is blended into a copy of ``score`` (float64, num_data), which is
+    returned: ``(score * pre + leaf) * post``, or ``/ post`` with ``divide``, each operation rounded
+    on its own. A tree with splits takes the blended traversal kernel of the dataset's row format, a
+    one-leaf tree the blended constant. ``grid`` caps the kernel's grid, so one block owns several
+    row tiles at small row counts."""
+    ds.construct()
+    s = np.ascontiguousarray(score, dtype=np.float64).ravel()
+    if s.size != ds.num_data():
+        raise ValueError(f"score has {s.size} values for {ds.num_data()} rows")
+    out = np.zeros(max(s.size, 1), dtype=np.float64)
+    dp = ctypes.POINTER(ctypes.c_double)
+    _check(_LIB.LGBM_DeviceTestBlendScore(
+        ds.handle, booster.handle, ctypes.c_int(int(tree)), s.ctypes.data_as(dp), ctypes.c_double(float(pre)),
+        ctypes.c_double(float(post)), ctypes.c_int(1 if divide else 0), ctypes.c_int(int(grid or 0)),
+        out.ctypes.data_as(dp)))
     return out[:s.size]
 
 

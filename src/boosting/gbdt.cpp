@@ -240,8 +240,9 @@ void GBDT::UpdateScore(const Tree* tree, int k) {
   } else {
     double* s = train_score_.data() + static_cast<size_t>(k) * num_data_;
     // a host learner adds the in-bag rows from its partition, the out-of-bag rows walk the tree;
-    // a device learner scored on the host (boosting=rf, DART with LGAP_DEVICE_DART=0 or linear
-    // leaves) walks every row itself, so a second pass over the out-of-bag rows would add the tree twice
+    // a device learner scored on the host (DART with LGAP_DEVICE_DART=0 or linear leaves, RF with
+    // LGAP_DEVICE_RF=0 or what RF::Init keeps on the host) walks every row itself, so a second pass
+    // over the out-of-bag rows would add the tree twice
     if (sampler_->active() && !learner_->OwnsScore()) {
       learner_->AddPredictionToScore(tree, s);
       const auto& bag = sampler_->bag_indices();
@@ -312,7 +313,8 @@ bool GBDT::TrainOneIterDevice(const DeviceGradView& view) {
   ScopedTimer timer("GBDT::TrainOneIter");
   if (!device_mode_) {
     Log::Fatal("update_device needs a booster that keeps its score and gradients on the GPU (device_type=gpu, "
-               "boosting=gbdt, a configuration the device learner serves); use Booster.update(fobj=...) here");
+               "boosting=gbdt or a device-scored boosting=dart / rf, a configuration the device learner serves); use "
+               "Booster.update(fobj=...) here");
   }
   if (objective_ != nullptr) {
     Log::Fatal("update_device: cannot use custom gradients with a built-in objective (set objective=custom, or call "
@@ -596,8 +598,9 @@ void GBDT::GetPredictAt(int data_idx, double* out, int64_t* out_len) {
 
 void GBDT::GetRawScoreDevice(int data_idx, int64_t* out_len, int* out_device, double* out_dev) {
   if (!device_mode_) {
-    Log::Fatal("raw_score_device needs a booster that keeps its scores on the GPU (device_type=gpu, boosting=gbdt, a "
-               "configuration the device learner serves); use Booster.update(fobj=...) / eval, which read host scores");
+    Log::Fatal("raw_score_device needs a booster that keeps its scores on the GPU (device_type=gpu, boosting=gbdt or a "
+               "device-scored boosting=dart / rf, a configuration the device learner serves); use "
+               "Booster.update(fobj=...) / eval, which read host scores");
   }
   if (data_idx < 0 || static_cast<size_t>(data_idx) > valid_score_.size()) Log::Fatal("Invalid data index %d", data_idx);
   const data_size_t n = data_idx == 0 ? num_data_ : valid_data_[data_idx - 1]->num_data();
@@ -857,10 +860,23 @@ void RF::Init(const Config* config, const Dataset* train_data, const ObjectiveFu
     }
   }
   GBDT::Init(config, train_data, objective, training_metrics);
-  device_mode_ = false;  // RF averages scores on host
   average_output_ = true;
   shrinkage_rate_ = 1.0;
   if (objective_ == nullptr) Log::Fatal("RF mode do not support custom objective function, please use built-in objectives.");
+  // A learner that owns the score keeps RF's running average there (TrainOneIterOnDevice). What
+  // it does not serve stays on the host, as before:
+  if (device_mode_) {
+    const char* why = nullptr;
+    if (!DeviceRfMode()) why = "LGAP_DEVICE_RF=0";
+    else if (config->linear_tree) why = "linear_tree";  // the leaves' raw values are on the host
+    // RF renews against the constant init score; the device renewal reads the device score
+    else if (objective_->IsRenewTreeOutput()) why = "the objective renews leaf outputs";
+    // GOSS rescales the gradients in place, and RF's are computed once
+    else if (config->data_sample_strategy == "goss") why = "data_sample_strategy=goss";
+    else if (num_init_models_ > 0) why = "continued from an init model";
+    else if (Network::num_machines() > 1) why = "more than one machine";
+    if (why != nullptr) LeaveDeviceMode(why);
+  }
   init_scores_.assign(num_tree_per_iteration_, 0.0);
   for (int k = 0; k < num_tree_per_iteration_; ++k) init_scores_[k] = BoostFromAverage(k, false);
   std::vector<double> tmp(static_cast<size_t>(num_data_) * num_tree_per_iteration_);
@@ -868,9 +884,110 @@ void RF::Init(const Config* config, const Dataset* train_data, const ObjectiveFu
     std::fill(tmp.begin() + static_cast<size_t>(k) * num_data_, tmp.begin() + static_cast<size_t>(k + 1) * num_data_,
               init_scores_[k]);
   objective_->GetGradients(tmp.data(), gradients_.data(), hessians_.data());
+  // RF's gradients never change: they go to the device once, not once per tree
+  if (device_mode_) learner_->DeviceSetGradients(gradients_.data(), hessians_.data(), num_tree_per_iteration_);
+  grads_kept_ = grads_dirty_ = false;
+}
+
+// From here on the score, its averaging and the metrics are the host's. Scores the device holds
+// come back first.
+void RF::LeaveDeviceMode(const char* why) {
+  SyncTrainScoreFromDevice();
+  for (size_t d = 0; d < valid_dev_.size(); ++d) {
+    (void)ValidScore(d);
+    valid_dev_[d] = -1;
+  }
+  device_mode_ = false;
+  Log::Info("RF: the score and its averaging stay on the host (%s)", why);
+}
+
+void RF::MergeFrom(const GBDT* other) {
+  GBDT::MergeFrom(other);
+  if (device_mode_ && num_init_models_ > 0) LeaveDeviceMode("continued from an init model");
+}
+
+// The device gradients as RF::Init computed them, before an iteration's trees. Quantized training
+// de-quantizes them in place (one tree's rounding would feed the next), so they are restored from
+// a copy kept on the device; quant_round_ advances as on the host path, which uploads them afresh.
+void RF::PrepareDeviceGradients() {
+  const int K = num_tree_per_iteration_;
+  if (!config_->use_quantized_grad) {
+    if (grads_dirty_) learner_->DeviceSetGradients(gradients_.data(), hessians_.data(), K);
+    grads_dirty_ = false;
+    return;
+  }
+  if (!grads_kept_) {
+    if (grads_dirty_) learner_->DeviceSetGradients(gradients_.data(), hessians_.data(), K);
+    learner_->DeviceKeepGradients(K);
+    grads_kept_ = true;
+  } else {
+    learner_->DeviceRestoreGradients(K);
+  }
+  grads_dirty_ = true;
+}
+
+// One blended update per score where the host path makes three passes and a host traversal:
+// s = (s * pre + tree(row)) * post (or / post), the training score and every validation set.
+void RF::BlendIntoScores(const Tree* tree, int k, const ScoreBlend& b) {
+  ScopedTimer t("RF::BlendIntoScores");
+  learner_->DeviceBlendTreeIntoScore(tree, k, b);
+  train_score_stale_ = true;
+  for (size_t d = 0; d < valid_score_.size(); ++d) {
+    if (valid_dev_[d] >= 0) {
+      learner_->DeviceBlendTreeIntoValid(valid_dev_[d], tree, k, b);
+      valid_stale_[d] = 1;
+      continue;
+    }
+    // a set that stayed on the host: the host arithmetic
+    const data_size_t n = valid_data_[d]->num_data();
+    double* vs = valid_score_[d].data() + static_cast<size_t>(k) * n;
+    for (data_size_t i = 0; i < n; ++i) vs[i] *= b.pre;
+    tree->AddPredictionToScore(*valid_data_[d], n, vs);
+    if (b.divide) {
+      for (data_size_t i = 0; i < n; ++i) vs[i] /= b.post;
+    } else {
+      for (data_size_t i = 0; i < n; ++i) vs[i] *= b.post;
+    }
+  }
+}
+
+bool RF::TrainOneIterOnDevice() {
+  ScopedTimer timer("RF::TrainOneIter(device)");
+  // the row sample, as GBDT::TrainWithGradients draws it
+  int plan = kSampleHost;
+  if (config_->device_sampling && learner_->SupportsDeviceSampling()) plan = sampler_->PlanDevice(iter_);
+  if (plan != kSampleHost) {
+    learner_->DeviceSample(plan, iter_);
+  } else {
+    const bool rebag = sampler_->Bagging(iter_, gradients_.data(), hessians_.data());
+    if (rebag) {
+      if (sampler_->active()) learner_->SetBaggingData(sampler_->bag_indices().data(), sampler_->bag_cnt());
+      else learner_->SetBaggingData(nullptr, num_data_);
+    }
+  }
+  PrepareDeviceGradients();
+  // the host's mult(k, iter_), UpdateScore, mult(k, 1.0 / (iter_ + 1))
+  const ScoreBlend blend{static_cast<double>(iter_), 1.0 / (iter_ + 1), false};
+  for (int k = 0; k < num_tree_per_iteration_; ++k) {
+    std::unique_ptr<Tree> tree = std::make_unique<Tree>(2);
+    if (class_need_train_[k]) tree = learner_->DeviceTrain(k, false);
+    if (tree->num_leaves() > 1) {
+      if (std::fabs(init_scores_[k]) > kEpsilon) tree->AddBias(init_scores_[k]);
+      BlendIntoScores(tree.get(), k, blend);
+    } else if (models_.size() < static_cast<size_t>(num_tree_per_iteration_)) {
+      double out = 0.0;
+      if (!class_need_train_[k]) out = objective_->BoostFromScore(k);
+      tree = ConstantTree(out, num_data_, config_->linear_tree);
+      BlendIntoScores(tree.get(), k, blend);
+    }
+    models_.push_back(std::move(tree));
+  }
+  ++iter_;
+  return false;
 }
 
 bool RF::TrainOneIter(const score_t*, const score_t*) {
+  if (device_mode_) return TrainOneIterOnDevice();
   const bool rebag = sampler_->Bagging(iter_, gradients_.data(), hessians_.data());
   if (rebag) {
     if (sampler_->active()) learner_->SetBaggingData(sampler_->bag_indices().data(), sampler_->bag_cnt());
@@ -915,6 +1032,20 @@ bool RF::TrainOneIter(const score_t*, const score_t*) {
 
 void RF::RollbackOneIter() {
   if (iter_ <= 0) return;
+  if (device_mode_) {
+    // the operations below, division included, as one blend per score; the validation sets
+    // are rolled back too, as the reference's RollbackOneIter does (the host path here leaves
+    // them: docs/COMPONENTS.md, Known gaps)
+    const ScoreBlend blend{static_cast<double>(iter_), iter_ > 1 ? static_cast<double>(iter_ - 1) : 1.0, iter_ > 1};
+    for (int k = 0; k < num_tree_per_iteration_; ++k) {
+      const size_t t = static_cast<size_t>(iter_ - 1) * num_tree_per_iteration_ + k;
+      models_[t]->Shrinkage(-1.0);
+      BlendIntoScores(models_[t].get(), k, blend);
+    }
+    for (int k = 0; k < num_tree_per_iteration_; ++k) models_.pop_back();
+    --iter_;
+    return;
+  }
   for (int k = 0; k < num_tree_per_iteration_; ++k) {
     const size_t t = static_cast<size_t>(iter_ - 1) * num_tree_per_iteration_ + k;
     models_[t]->Shrinkage(-1.0);

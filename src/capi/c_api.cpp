@@ -1538,6 +1538,18 @@ int LGBM_DeviceTestForestScore(DatasetHandle handle, BoosterHandle booster, cons
   API_END();
 }
 
+// Direct test of the blended score update (device_api.h TestBlendScore)
+int LGBM_DeviceTestBlendScore(DatasetHandle handle, BoosterHandle booster, int tree_idx, const double* score,
+                              double pre, double post, int divide, int grid, double* out) {
+  API_BEGIN();
+  Config cfg = ParseConfig("");
+  cfg.device_type = "gpu";
+  const int32_t idx = tree_idx;
+  const std::vector<const Tree*> trees = ForestTreesOf(booster, &idx, 1);
+  device::TestBlendScore(D(handle)->ds.get(), cfg, trees[0], score, pre, post, divide != 0, grid, out);
+  API_END();
+}
+
 int LGBM_DeviceTestForestRuns(BoosterHandle booster, const int32_t* tree_idx, int num_trees, int32_t* out_run_trees,
                               int32_t* out_run_bytes, int* out_num_runs, int* out_budget) {
   API_BEGIN();

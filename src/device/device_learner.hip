@@ -91,6 +91,7 @@
 #include <vector>
 
 #include "device/grad_kernels.h"
+#include "device/blend_kernels.h"
 #include "device/hip_common.h"
 #include "device/leaf_kernels.h"
 #include "device/metric_eval.h"
@@ -731,7 +732,7 @@ class DeviceTreeLearner : public TreeLearner {
   void DeviceComputeGradients(const ObjectiveFunction* obj) override {
     ScopedTimer timer("Device::ComputeGradients");
     PrepareObjective(obj);
-    if (pend_.on && pend_.k == 0 && K_ == 1 && obj->device_kind() == DeviceGradKind::kPointwise) {
+    if (pend_.on && !pend_.blended && pend_.k == 0 && K_ == 1 && obj->device_kind() == DeviceGradKind::kPointwise) {
       // the deferred leaf add of the last tree, fused with this gradient pass
       pend_.on = false;
       LaunchLeafMapAddGrad(leaf_map_.get(), pend_lv_.get(), pend_.nl, N_, score_.get(), *obj->pointwise(), label_.get(),
@@ -783,6 +784,18 @@ class DeviceTreeLearner : public TreeLearner {
     for (size_t i = 0; i < n; ++i) p[i] = make_float2(g[i], h[i]);
     HIP_CHECK(hipMemcpyAsync(gh_.get(), p, n * sizeof(float2), hipMemcpyHostToDevice, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+
+  void DeviceKeepGradients(int num_class) override {
+    const size_t n = static_cast<size_t>(num_class) * N_;
+    if (gh_.size() < n) Log::Fatal("DeviceKeepGradients: %zu gradients on the device, %zu asked for", gh_.size(), n);
+    gh_kept_.Resize(n);
+    HIP_CHECK(hipMemcpyAsync(gh_kept_.get(), gh_.get(), n * sizeof(float2), hipMemcpyDeviceToDevice, stream_));
+  }
+  void DeviceRestoreGradients(int num_class) override {
+    const size_t n = static_cast<size_t>(num_class) * N_;
+    if (gh_kept_.size() < n || gh_.size() < n) Log::Fatal("DeviceRestoreGradients: no kept copy of %zu gradients", n);
+    HIP_CHECK(hipMemcpyAsync(gh_.get(), gh_kept_.get(), n * sizeof(float2), hipMemcpyDeviceToDevice, stream_));
   }
 
   void DeviceGetGradients(std::vector<score_t>* g, std::vector<score_t>* h) const override {
@@ -952,6 +965,68 @@ class DeviceTreeLearner : public TreeLearner {
     TraverseTree(tree, rowbins_.get(), N_, s);
   }
 
+  // score = blend(score, tree(row)) (ScoreBlend; boosting=rf's running average), routed as
+  // DeviceAddTreeToScore: the tree just grown on the frontier through its leaf map, the blend
+  // pending until the score is read; a one-leaf tree as a constant; any other tree walked.
+  void DeviceBlendTreeIntoScore(const Tree* tree, int k, const ScoreBlend& b) override {
+    ScopedTimer timer("Device::BlendTreeIntoScore");
+    FlushScore();
+    if (tree->is_linear()) Log::Fatal("DeviceBlendTreeIntoScore: linear leaves are blended on the host");
+    double* s = score_.get() + static_cast<size_t>(k) * N_;
+    const bool fresh = tree == last_trained_;
+    last_trained_ = nullptr;
+    if (tree->num_leaves() > 1 && fresh && frontier_ && (!use_bag_ || oob_ok_) && LeafMapScore(tree, k, &b)) return;
+    BlendTree(tree, rowbins_.get(), N_, s, b, 0);
+  }
+  void DeviceBlendTreeIntoValid(int id, const Tree* tree, int k, const ScoreBlend& b) override {
+    ScopedTimer timer("Device::BlendTreeIntoValid");
+    if (tree->is_linear()) Log::Fatal("DeviceBlendTreeIntoValid: linear leaves are blended on the host");
+    DevValid& v = *valid_[id];
+    BlendTree(tree, v.rowbins.get(), v.n, v.score.get() + static_cast<size_t>(k) * v.n, b, 0);
+  }
+
+  // s[i] = blend(s[i], tree(row i)) over packed rows of the training layout (training or
+  // validation set), never through the leaf map
+  void BlendTree(const Tree* tree, const uint32_t* rowbins, int n, double* s, const ScoreBlend& b, int grid_cap) {
+    if (tree->num_leaves() <= 1) {
+      // the host leaves out the add of a one-leaf tree of value zero (Tree::AddPredictionToScore);
+      // adding -0.0 is that: x + (-0.0) == x for every x, either zero included
+      const double v = tree->LeafOutput(0);
+      LaunchBlendConstant(s, n, v != 0.0 ? v : -0.0, b, stream_);
+      return;
+    }
+    if (tree->num_leaves() > 32767) {
+      // past the compact node format (k_add_tree): not fused. A scale pass, the plain add and a
+      // scale pass round exactly as the fused kernels do, at three passes over the score.
+      LaunchBlendScale(s, n, b.pre, false, stream_);
+      TraverseTree(tree, rowbins, n, s);
+      LaunchBlendScale(s, n, b.post, b.divide, stream_);
+      return;
+    }
+    ScopedTimer timer("Device::BlendTraverse");
+    const CompactLayout z = CompactTreeLayout(tree);
+    PackCompactTree(tree, data_, tree_ring_.Begin(z.total), z);
+    const CompactTreeDev t = CompactTreeAt(tree_ring_.Commit(stream_), z, tree->num_leaves());
+    // the row copies TraverseTreeCompact chooses between
+    if (rowbins == rowbins_.get() && n == N_ && stride_dw_ > 16 && colbins_.size() >= static_cast<size_t>(G_) * N_ * width_) {
+      LaunchBlendTraverseCols(colbins_.get(), width_, n, t, b, s, num_cu_, grid_cap, stream_);
+    } else if (nib_ && rowbins == rowbins_.get() && n == N_) {
+      LaunchBlendTraverse(rowbins4_.get(), stride4_dw_, 0, n, t, b, s, num_cu_, grid_cap, stream_);
+    } else {
+      LaunchBlendTraverse(rowbins, StrideOf(rowbins), width_, n, t, b, s, num_cu_, grid_cap, stream_);
+    }
+  }
+
+  // ops.blend_score: `score` (N_ values) uploaded as a one-class training score, one tree blended
+  // in by the traversal route (a one-leaf tree: the blended constant), the score read back
+  void TestBlendScore(const Tree* tree, const double* score, const ScoreBlend& b, int grid_cap, double* out) {
+    DeviceInitScore(std::vector<double>(score, score + N_), 1);
+    BlendTree(tree, rowbins_.get(), N_, score_.get(), b, grid_cap);
+    std::vector<double> res;
+    DeviceGetScore(&res);
+    std::copy(res.begin(), res.end(), out);
+  }
+
   // Several trees into the training score (DART's dropped trees), each row adding its class's
   // trees in list order: one single-tree traversal per tree, or with LGAP_DEVICE_DART=forest one
   // k_traverse_forest launch per class.
@@ -1030,7 +1105,8 @@ class DeviceTreeLearner : public TreeLearner {
   // The map is built here; the add itself is deferred (pend_) into the next pointwise
   // gradient pass, or flushed by the first reader of the score (FlushScore). Uploads go
   // through the traversal's staging ring (no host wait).
-  bool LeafMapScore(const Tree* tree, int k) {
+  // blend: the pending update blends the leaf values in (ScoreBlend) instead of adding them.
+  bool LeafMapScore(const Tree* tree, int k, const ScoreBlend* blend = nullptr) {
     const int nl = tree->num_leaves();
     const bool bag = use_bag_;
     const int nseg = nl + (bag ? 1 : 0);  // (bag: the out-of-bag rows, placeholder leaf nl)
@@ -1109,6 +1185,8 @@ class DeviceTreeLearner : public TreeLearner {
     pend_.on = true;
     pend_.k = k;
     pend_.nl = nseg;
+    pend_.blended = blend != nullptr;
+    if (blend != nullptr) pend_.blend = *blend;
     return true;
   }
 
@@ -1116,6 +1194,12 @@ class DeviceTreeLearner : public TreeLearner {
   void FlushScore() const {
     if (!pend_.on) return;
     pend_.on = false;
+    if (pend_.blended) {
+      ScopedTimer timer("Device::BlendLeafMap");
+      LaunchBlendLeafMapAdd(leaf_map_.get(), pend_lv_.get(), pend_.nl, N_, pend_.blend,
+                            score_.get() + static_cast<size_t>(pend_.k) * N_, num_cu_, stream_);
+      return;
+    }
     LaunchLeafMapAdd(leaf_map_.get(), pend_lv_.get(), pend_.nl, N_, score_.get() + static_cast<size_t>(pend_.k) * N_,
                      num_cu_, stream_);
   }
@@ -3990,6 +4074,7 @@ class DeviceTreeLearner : public TreeLearner {
   DevBuf<uint32_t> rowbins_;
   DevBuf<uint8_t> colbins_;
   DevBuf<float2> gh_;
+  DevBuf<float2> gh_kept_;  // DeviceKeepGradients: the copy DeviceRestoreGradients reads
   DevBuf<double> score_;
   DevBuf<float> label_, weight_, aux_;
   static_assert(kFrontierIdx <= kLeafIdxBufs, "leaf renewal addresses every index buffer");
@@ -4095,6 +4180,8 @@ class DeviceTreeLearner : public TreeLearner {
   struct PendingAdd {
     bool on = false;
     int k = 0, nl = 0;
+    bool blended = false;  // blend it in (DeviceBlendTreeIntoScore) instead of adding it
+    ScoreBlend blend{0.0, 1.0, false};
   };
   mutable PendingAdd pend_;  // a tree's leaf add not yet applied to score_ (FlushScore)
   std::vector<uint8_t> leaf_desc_;  // LeafMapScore: per-leaf row direction
@@ -4330,6 +4417,16 @@ void TestForestScore(const Dataset* data, const Config& config, const Tree* cons
     refs.push_back({own.back().get(), 0});
   }
   learner.TestForestScore(refs, score, grid_cap, per_tree, out, info);
+}
+
+void TestBlendScore(const Dataset* data, const Config& config, const Tree* tree, const double* score, double pre,
+                    double post, bool divide, int grid_cap, double* out) {
+  if (DeviceCount() <= 0) Log::Fatal("TestBlendScore: no AMD GPU visible to HIP");
+  if (grid_cap < 0) Log::Fatal("TestBlendScore: grid %d", grid_cap);
+  if (tree->is_linear()) Log::Fatal("TestBlendScore: the tree has linear leaves");
+  DeviceTreeLearner learner(&config, "serial");
+  learner.Init(data, false);
+  learner.TestBlendScore(tree, score, ScoreBlend{pre, post, divide}, grid_cap, out);
 }
 
 bool TestQuantize(const Dataset* data, const Config& config, bool const_hess, const float* grad, const float* hess,

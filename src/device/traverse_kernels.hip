@@ -10,56 +10,13 @@
 
 #include "device/hip_common.h"
 #include "device/linear_kernels.h"
+#include "device/traverse_device.h"
 #include "lgap/log.h"
 #include "lgap/pointwise.h"
 
 namespace lgap {
 namespace device {
 namespace {
-
-constexpr int kTThreads = 256;
-constexpr int kTRowsPerThread = 2;
-constexpr int kTRows = kTThreads * kTRowsPerThread;
-constexpr int kTMaxDw = 16;  // wider rows read global memory directly
-
-// Row-walk grid: 8 blocks per CU, grid-stride over the chunks
-int TraverseGrid(long long n, int num_cu) {
-  const long long chunks = (n + kTRows - 1) / kTRows;
-  return static_cast<int>(std::max<long long>(1, std::min<long long>(chunks, static_cast<long long>(num_cu) * 8)));
-}
-
-template <int W>
-__device__ __forceinline__ uint32_t GroupBin(const uint8_t* row, int g) {
-  if (W == 0) return (row[g >> 1] >> ((g & 1) * 4)) & 0xFu;  // 4-bit rows
-  return W == 1 ? row[g] : reinterpret_cast<const uint16_t*>(row)[g];
-}
-
-__device__ __forceinline__ bool CatLeft(const TCat& c, const uint32_t* bits, uint32_t gb) {
-  const int local = static_cast<int>(gb) - c.offset;
-  uint32_t b;
-  if (local < 0 || local >= c.num_bin - 1) b = static_cast<uint32_t>(c.mfb);
-  else b = static_cast<uint32_t>(local < c.mfb ? local : local + 1);
-  const uint32_t w = b >> 5;
-  return static_cast<int>(w) < c.nwords && ((bits[c.begin + w] >> (b & 31u)) & 1u);
-}
-
-// One level of a walk: the child of node `node` (its packed form `nd`) that a row whose group bin
-// is `gb` goes to (>= 0: a node, < 0: ~leaf). The group-bin predicate of traverse_kernels.h, the
-// one copy every traversal kernel here calls.
-__device__ __forceinline__ int NodeStep(const TNode& nd, uint32_t gb, const TCat* __restrict__ cats,
-                                        const uint32_t* __restrict__ cat_bits, int node) {
-  bool left;
-  if (nd.flags & kTCat) {
-    left = CatLeft(cats[node], cat_bits, gb);
-  } else if (gb < nd.lo || gb > nd.hi) {
-    left = (nd.flags & kTOutLeft) != 0;
-  } else if (static_cast<int>(gb) == nd.gmiss) {
-    left = (nd.flags & kTDefaultLeft) != 0;
-  } else {
-    left = gb <= nd.tg;
-  }
-  return left ? nd.left : nd.right;
-}
 
 // a linear leaf's value for row `row` (reference linear tree Predict: the leaf's constant output
 // when any of the model's features is NaN)

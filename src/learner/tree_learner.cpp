@@ -43,6 +43,17 @@ DeviceDart DeviceDartMode() {
   return mode;
 }
 
+bool DeviceRfMode() {
+  static const bool device = [] {
+    const char* e = std::getenv("LGAP_DEVICE_RF");
+    if (e == nullptr || std::strcmp(e, "1") == 0) return true;
+    if (std::strcmp(e, "0") == 0) return false;
+    Log::Fatal("LGAP_DEVICE_RF: unknown value '%s' (1 or 0)", e);
+    return true;
+  }();
+  return device;
+}
+
 // Only a learner that owns the score on the device serves these (the boosting loop refuses
 // earlier, with the advice to use Booster.update; reaching them is a routing bug).
 void TreeLearner::DeviceSetGradientsFromDevice(const DeviceGradView&) {
