@@ -409,6 +409,25 @@ LIGHTGBM_C_EXPORT int LGBM_DeviceSampleRows(int mode, int32_t num_rows, int num_
                                             double neg_fraction, double top_rate, double other_rate,
                                             int bagging_seed, uint32_t goss_seed, int rounds, int32_t* out_rows,
                                             int32_t* out_count);
+// The same kernels for a direct test: also mode 4, bagging by query (query_sizes[num_queries] sum to
+// num_rows; the per-query streams are advanced after every round as the learner does), and with_oob
+// != 0 the out-of-bag list. out_rows and out_oob (may be null without with_oob), both [num_rows], are
+// filled with -1 before every round and returned whole: the kept rows in out_rows[0 .. *out_total),
+// the others in out_oob[0 .. num_rows - *out_total), -1 wherever the kernels did not write.
+LIGHTGBM_C_EXPORT int LGBM_DeviceTestSampleRows(int mode, int32_t num_rows, int num_class, float* grad, float* hess,
+                                                const float* label, const int32_t* query_sizes, int32_t num_queries,
+                                                double fraction, double pos_fraction, double neg_fraction,
+                                                double top_rate, double other_rate, int bagging_seed,
+                                                uint32_t goss_seed, int rounds, int with_oob, int32_t* out_rows,
+                                                int32_t* out_oob, int32_t* out_total);
+// The host sampler those kernels reproduce (no GPU needed): a SampleStrategy with `parameters` over the
+// Dataset, Bagging(iters[i], grad, hess) for every i in order. grad/hess (num_class * num_data,
+// class-major) are scaled in place by GOSS. out_indices [num_data]: bag_indices(), the bag followed by
+// the out-of-bag rows; *out_bag_cnt: bag_cnt(); *out_drawn: whether the last call drew a bag (if none
+// ever did, every row is used and out_indices holds no list).
+LIGHTGBM_C_EXPORT int LGBM_TestHostSampleRows(DatasetHandle handle, const char* parameters, int num_class,
+                                              const int32_t* iters, int num_iters, float* grad, float* hess,
+                                              int32_t* out_indices, int32_t* out_bag_cnt, int* out_drawn);
 LIGHTGBM_C_EXPORT int LGBM_DeviceCommGetUniqueId(char* out, int64_t buffer_len, int64_t* out_len);
 LIGHTGBM_C_EXPORT int LGBM_DeviceCommInit(const char* unique_id, int64_t id_len, int num_ranks, int rank,
                                           int device_id);

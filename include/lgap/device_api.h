@@ -137,6 +137,15 @@ void TestLinearGram(const float* raw, int N, int F, const float* grad, const flo
 int SampleRowsOnDevice(int mode, int num_rows, int num_class, float* grad, float* hess, const float* label,
                        double fraction, double pos_fraction, double neg_fraction, double top_rate, double other_rate,
                        int bagging_seed, uint32_t goss_seed, int rounds, int* out_rows);
+// The same kernels for a direct test (LGBM_DeviceTestSampleRows, tests/test_sample_kernels.py): also
+// mode 4, bagging by query, with row_unit / num_units built from query_sizes[num_queries] and
+// LaunchSampleAdvanceUnits after every round as the learner launches it; with_oob allocates the
+// out-of-bag list. out_rows and out_oob (both [num_rows]) are filled with -1 before every round and
+// returned whole, so writes past the counts show.
+int TestSampleRows(int mode, int num_rows, int num_class, float* grad, float* hess, const float* label,
+                   const int* query_sizes, int num_queries, double fraction, double pos_fraction, double neg_fraction,
+                   double top_rate, double other_rate, int bagging_seed, uint32_t goss_seed, int rounds, bool with_oob,
+                   int* out_rows, int* out_oob);
 
 // Feature binning on the device (bin_kernels.hip): packs `nrow` rows of a dense row-major
 // matrix (fp32 / fp64) into `ds`'s packed group-bin layout (its mappers and EFB groups),

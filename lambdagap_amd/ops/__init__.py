@@ -15,7 +15,7 @@ from ..basic import _LIB, Booster, Dataset, _check
 
 __all__ = ["group_layout", "group_bins", "device_histogram", "device_sample_rows", "booster_gradients",
            "frontier_histogram", "frontier_partition", "quantize_gradients", "linear_gram", "forest_score",
-           "forest_runs", "blend_score"]
+           "forest_runs", "blend_score", "device_sample_test", "host_sample_rows"]
 
 
 def group_layout(ds: Dataset) -> Tuple[int, int, int, np.ndarray]:
@@ -81,6 +81,64 @@ def device_sample_rows(mode: str, grad: np.ndarray, hess: np.ndarray, label: Opt
         ctypes.c_double(other_rate), ctypes.c_int(bagging_seed), ctypes.c_uint32(goss_seed), ctypes.c_int(rounds),
         rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(cnt)))
     return rows[:cnt.value].copy(), g, h
+
+
+def device_sample_test(mode: str, grad: np.ndarray, hess: np.ndarray, label: Optional[np.ndarray] = None,
+                       query_sizes: Optional[np.ndarray] = None, num_class: int = 1, fraction: float = 1.0,
+                       pos_fraction: float = 1.0, neg_fraction: float = 1.0, top_rate: float = 0.2,
+                       other_rate: float = 0.1, bagging_seed: int = 3, goss_seed: int = 0, rounds: int = 1,
+                       oob: bool = True) -> Tuple[np.ndarray, Optional[np.ndarray], int, np.ndarray, np.ndarray]:
+    """The HIP sampling kernels for a direct test: ``device_sample_rows`` plus ``mode="query"`` (bagging
+    by query with ``query_sizes``, the query streams advanced after every round) and the out-of-bag list.
+
+    Returns (out [n], oob [n] or None, total, grad, hess): both index buffers whole, filled with -1
+    before every round, so the kept rows are ``out[:total]``, the others ``oob[:n - total]`` and
+    everything behind them is -1 unless a kernel wrote past its count."""
+    g = np.array(grad, dtype=np.float32, copy=True).ravel()
+    h = np.array(hess, dtype=np.float32, copy=True).ravel()
+    n = g.size // num_class
+    lab = None if label is None else np.ascontiguousarray(label, dtype=np.float32)
+    qs = None if query_sizes is None else np.ascontiguousarray(query_sizes, dtype=np.int32)
+    out = np.zeros(max(n, 1), dtype=np.int32)
+    out_oob = np.zeros(max(n, 1), dtype=np.int32) if oob else None
+    total = ctypes.c_int32(0)
+    fp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)
+    _check(_LIB.LGBM_DeviceTestSampleRows(
+        ctypes.c_int({**_SAMPLE_MODES, "query": 4}[mode]), ctypes.c_int32(n), ctypes.c_int(num_class),
+        g.ctypes.data_as(fp), h.ctypes.data_as(fp), None if lab is None else lab.ctypes.data_as(fp),
+        None if qs is None else qs.ctypes.data_as(ip), ctypes.c_int32(0 if qs is None else qs.size),
+        ctypes.c_double(fraction), ctypes.c_double(pos_fraction), ctypes.c_double(neg_fraction),
+        ctypes.c_double(top_rate), ctypes.c_double(other_rate), ctypes.c_int(bagging_seed),
+        ctypes.c_uint32(goss_seed), ctypes.c_int(rounds), ctypes.c_int(int(oob)), out.ctypes.data_as(ip),
+        None if out_oob is None else out_oob.ctypes.data_as(ip), ctypes.byref(total)))
+    return out[:n], None if out_oob is None else out_oob[:n], total.value, g, h
+
+
+def host_sample_rows(ds: Dataset, params: dict, grad: np.ndarray, hess: np.ndarray, iters, num_class: int = 1
+                     ) -> Tuple[np.ndarray, np.ndarray, bool, np.ndarray, np.ndarray]:
+    """The host sampler (SampleStrategy) with ``params`` over a constructed Dataset: ``Bagging(iter, grad,
+    hess)`` for every iteration of ``iters``, no GPU needed.
+
+    Returns (bag, out-of-bag, drawn, grad, hess): the rows of the last bag and the others, both as the
+    sampler lists them, whether the last call drew a bag (False: every row is used, both lists empty),
+    and the gradients, which GOSS has scaled."""
+    ds.construct()
+    n = ds.num_data()
+    g = np.array(grad, dtype=np.float32, copy=True).ravel()
+    h = np.array(hess, dtype=np.float32, copy=True).ravel()
+    if g.size != num_class * n or h.size != num_class * n:
+        raise ValueError(f"host_sample_rows: {g.size} gradients for {num_class} x {n} rows")
+    it = np.ascontiguousarray(iters, dtype=np.int32).ravel()
+    idx = np.zeros(max(n, 1), dtype=np.int32)
+    cnt, drawn = ctypes.c_int32(0), ctypes.c_int(0)
+    fp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)
+    _check(_LIB.LGBM_TestHostSampleRows(ds.handle, ctypes.c_char_p(_param_str(params)), ctypes.c_int(num_class),
+                                        it.ctypes.data_as(ip), ctypes.c_int(it.size), g.ctypes.data_as(fp),
+                                        h.ctypes.data_as(fp), idx.ctypes.data_as(ip), ctypes.byref(cnt),
+                                        ctypes.byref(drawn)))
+    if not drawn.value:
+        return idx[:0].copy(), idx[:0].copy(), False, g, h
+    return idx[:cnt.value].copy(), idx[cnt.value:n].copy(), True, g, h
 
 
 def booster_gradients(booster: Booster) -> Tuple[np.ndarray, np.ndarray]:

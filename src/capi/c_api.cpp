@@ -1575,6 +1575,34 @@ int LGBM_DeviceSampleRows(int mode, int32_t num_rows, int num_class, float* grad
   API_END();
 }
 
+// Direct test of the sampling kernels (device_api.h TestSampleRows) and its host twin
+int LGBM_DeviceTestSampleRows(int mode, int32_t num_rows, int num_class, float* grad, float* hess, const float* label,
+                              const int32_t* query_sizes, int32_t num_queries, double fraction, double pos_fraction,
+                              double neg_fraction, double top_rate, double other_rate, int bagging_seed,
+                              uint32_t goss_seed, int rounds, int with_oob, int32_t* out_rows, int32_t* out_oob,
+                              int32_t* out_total) {
+  API_BEGIN();
+  *out_total = device::TestSampleRows(mode, num_rows, num_class, grad, hess, label, query_sizes, num_queries, fraction,
+                                      pos_fraction, neg_fraction, top_rate, other_rate, bagging_seed, goss_seed,
+                                      rounds, with_oob != 0, out_rows, out_oob);
+  API_END();
+}
+
+int LGBM_TestHostSampleRows(DatasetHandle handle, const char* parameters, int num_class, const int32_t* iters,
+                            int num_iters, float* grad, float* hess, int32_t* out_indices, int32_t* out_bag_cnt,
+                            int* out_drawn) {
+  API_BEGIN();
+  const Config cfg = ParseConfig(parameters);
+  const Dataset* d = D(handle)->ds.get();
+  SampleStrategy s(&cfg, d, nullptr, std::max(1, num_class));
+  bool drawn = false;
+  for (int i = 0; i < num_iters; ++i) drawn = s.Bagging(iters[i], grad, hess);
+  std::copy(s.bag_indices().begin(), s.bag_indices().end(), out_indices);
+  *out_bag_cnt = s.bag_cnt();
+  *out_drawn = drawn ? 1 : 0;
+  API_END();
+}
+
 int LGBM_DeviceSynchronize() {
   API_BEGIN();
   device::DeviceSynchronize();

@@ -9,6 +9,7 @@
 // Two launches over the rows and no host round trip besides the final count.
 #include "device/sample_kernels.h"
 
+#include <algorithm>
 #include <vector>
 
 #include "device/hip_common.h"
@@ -290,10 +291,12 @@ void LaunchSampleScatter(const SampleArgs& a, hipStream_t s) {
   HIP_CHECK(hipGetLastError());
 }
 
-int SampleRowsOnDevice(int mode, int num_rows, int num_class, float* grad, float* hess, const float* label,
-                       double fraction, double pos_fraction, double neg_fraction, double top_rate, double other_rate,
-                       int bagging_seed, uint32_t goss_seed, int rounds, int* out_rows) {
-  if (mode < 1 || mode > 3) Log::Fatal("SampleRowsOnDevice: mode must be 1, 2 or 3");
+// The production launches over host arrays, in the learner's order (device_api.h)
+int TestSampleRows(int mode, int num_rows, int num_class, float* grad, float* hess, const float* label,
+                   const int* query_sizes, int num_queries, double fraction, double pos_fraction, double neg_fraction,
+                   double top_rate, double other_rate, int bagging_seed, uint32_t goss_seed, int rounds, bool with_oob,
+                   int* out_rows, int* out_oob) {
+  if (mode < 1 || mode > 4) Log::Fatal("TestSampleRows: mode must be 1, 2, 3 or 4");
   if (num_rows <= 0) return 0;
   const size_t n = static_cast<size_t>(num_rows), nk = n * std::max(1, num_class);
   const int nt = SampleTiles(num_rows);
@@ -301,20 +304,37 @@ int SampleRowsOnDevice(int mode, int num_rows, int num_class, float* grad, float
   for (size_t i = 0; i < nk; ++i) gh[i] = make_float2(grad ? grad[i] : 0.f, hess ? hess[i] : 0.f);
   std::vector<uint2> jt(kSampleRandBlock);
   BuildLcgJumpTable(jt.data());
-  std::vector<unsigned> st((n + kSampleRandBlock - 1) / kSampleRandBlock);
+  // one stream per 1024 units: rows, or queries when bagging by query
+  size_t units = n;
+  std::vector<int> rq;
+  if (mode == 4) {
+    if (!query_sizes || num_queries <= 0) Log::Fatal("TestSampleRows: bagging by query needs query sizes");
+    rq.reserve(n);
+    for (int q = 0; q < num_queries; ++q) {
+      if (query_sizes[q] < 0 || rq.size() + static_cast<size_t>(query_sizes[q]) > n) Log::Fatal("TestSampleRows: query sizes do not sum to the row count");
+      rq.insert(rq.end(), static_cast<size_t>(query_sizes[q]), q);
+    }
+    if (rq.size() != n) Log::Fatal("TestSampleRows: query sizes do not sum to the row count");
+    units = static_cast<size_t>(num_queries);
+  }
+  std::vector<unsigned> st((units + kSampleRandBlock - 1) / kSampleRandBlock);
   for (size_t b = 0; b < st.size(); ++b) st[b] = static_cast<unsigned>(bagging_seed + static_cast<int>(b));
   DevBuf<float2> d_gh;
   DevBuf<uint2> d_jump;
   DevBuf<unsigned> d_rng, d_sel(4 * static_cast<size_t>(nt));
-  DevBuf<int> d_cnt(nt), d_out(n), d_total(1);
+  DevBuf<int> d_cnt(nt), d_out(n), d_oob(with_oob ? n : 0), d_total(1), d_rq;
   DevBuf<float> d_label;
   d_gh.Upload(gh);
   d_jump.Upload(jt);
   d_rng.Upload(st);
   if (mode == 2) {
-    if (!label) Log::Fatal("SampleRowsOnDevice: balanced bagging needs labels");
+    if (!label) Log::Fatal("TestSampleRows: balanced bagging needs labels");
     d_label.Upload(label, n);
   }
+  if (mode == 4) d_rq.Upload(rq);
+  // -1 in every slot: whatever lies past the counts afterwards was never written
+  HIP_CHECK(hipMemsetAsync(d_out.get(), 0xFF, n * sizeof(int), 0));
+  if (with_oob) HIP_CHECK(hipMemsetAsync(d_oob.get(), 0xFF, n * sizeof(int), 0));
   SampleArgs a;
   a.mode = mode;
   a.N = num_rows;
@@ -328,26 +348,48 @@ int SampleRowsOnDevice(int mode, int num_rows, int num_class, float* grad, float
   a.label = d_label.get();
   a.gh = d_gh.get();
   a.rng = d_rng.get();
+  a.row_unit = d_rq.get();
+  a.num_units = mode == 4 ? num_queries : 0;
   a.jump = d_jump.get();
   a.tile_cnt = d_cnt.get();
   a.tile_sel = d_sel.get();
   a.out = d_out.get();
+  a.oob = with_oob ? d_oob.get() : nullptr;
   a.total = d_total.get();
   for (int r = 0; r < std::max(1, rounds); ++r) {
+    if (r > 0) {
+      HIP_CHECK(hipMemsetAsync(d_out.get(), 0xFF, n * sizeof(int), 0));
+      if (with_oob) HIP_CHECK(hipMemsetAsync(d_oob.get(), 0xFF, n * sizeof(int), 0));
+    }
     LaunchSampleCount(a, 0);
     LaunchSampleScatter(a, 0);
+    if (mode == 4) LaunchSampleAdvanceUnits(a, 0);
   }
   int total = 0;
   d_total.Download(&total, 1);
   HIP_CHECK(hipDeviceSynchronize());
-  if (total < 0 || total > num_rows) Log::Fatal("SampleRowsOnDevice: invalid count %d", total);
-  d_out.Download(out_rows, total);
+  if (total < 0 || total > num_rows) Log::Fatal("TestSampleRows: invalid count %d", total);
+  d_out.Download(out_rows, n);
+  if (with_oob) d_oob.Download(out_oob, n);
   d_gh.Download(gh.data(), nk);
   HIP_CHECK(hipDeviceSynchronize());
   for (size_t i = 0; i < nk; ++i) {
     if (grad) grad[i] = gh[i].x;
     if (hess) hess[i] = gh[i].y;
   }
+  return total;
+}
+
+int SampleRowsOnDevice(int mode, int num_rows, int num_class, float* grad, float* hess, const float* label,
+                       double fraction, double pos_fraction, double neg_fraction, double top_rate, double other_rate,
+                       int bagging_seed, uint32_t goss_seed, int rounds, int* out_rows) {
+  if (mode < 1 || mode > 3) Log::Fatal("SampleRowsOnDevice: mode must be 1, 2 or 3");
+  if (num_rows <= 0) return 0;
+  std::vector<int> rows(static_cast<size_t>(num_rows));
+  const int total = TestSampleRows(mode, num_rows, num_class, grad, hess, label, nullptr, 0, fraction, pos_fraction,
+                                   neg_fraction, top_rate, other_rate, bagging_seed, goss_seed, rounds, false,
+                                   rows.data(), nullptr);
+  std::copy(rows.begin(), rows.begin() + total, out_rows);
   return total;
 }
 
