@@ -17,6 +17,7 @@
 typedef void* DatasetHandle;
 typedef void* BoosterHandle;
 typedef void* FastConfigHandle;
+typedef void* DevicePredictorHandle;
 
 #define C_API_DTYPE_FLOAT32 (0)
 #define C_API_DTYPE_FLOAT64 (1)
@@ -190,6 +191,31 @@ LIGHTGBM_C_EXPORT int LGBM_BoosterTestPackedPredict(BoosterHandle handle, const 
                                                     int32_t nrow, int32_t ncol, int predict_type, int start_iteration,
                                                     int num_iteration, const char* parameter, int64_t* out_len,
                                                     double* out_result);
+// Test hook: the same result by the tree-parallel algorithm of the resident predictor's small-batch
+// kernels, in host loops (no GPU): every (row, tree) pair into a [tree][row] array, then the fold.
+LIGHTGBM_C_EXPORT int LGBM_BoosterTestPackedPredictTreeParallel(BoosterHandle handle, const void* data,
+                                                                int data_type, int32_t nrow, int32_t ncol,
+                                                                int predict_type, int start_iteration,
+                                                                int num_iteration, const char* parameter,
+                                                                int64_t* out_len, double* out_result);
+// A resident device predictor (Booster.device_predictor): the iterations LGBM_BoosterPredictForMatDevice
+// would select are packed and uploaded once and `parameter` is parsed once; every later call only
+// moves rows and launches. The predictor is a snapshot: later changes of the booster's trees do
+// not reach it. The booster must outlive it (its objective transforms NORMAL output).
+// tree_parallel_rows: batches of at most this many rows run the tree-parallel kernels (one work
+// item per row and tree), larger ones the row-parallel kernels; 0 never, -1 the measured default,
+// more than 65536 is an error. pred_early_stop=true and a process without a GPU return -1.
+LIGHTGBM_C_EXPORT int LGBM_BoosterDevicePredictorCreate(BoosterHandle handle, int start_iteration, int num_iteration,
+                                                        int tree_parallel_rows, const char* parameter,
+                                                        DevicePredictorHandle* out);
+// Arguments and results as LGBM_BoosterPredictForMatDevice's, PREDICT_CONTRIB refused. Calls on
+// one handle are serialised inside it.
+LIGHTGBM_C_EXPORT int LGBM_DevicePredictorPredict(DevicePredictorHandle handle, const void* data, int data_type,
+                                                  int32_t nrow, int32_t ncol, int predict_type, int data_on_device,
+                                                  int out_on_device, int64_t* out_len, double* out_result);
+// The kernel family of the last call that launched: 0 row-parallel, 1 tree-parallel, -1 none yet.
+LIGHTGBM_C_EXPORT int LGBM_DevicePredictorLastPath(DevicePredictorHandle handle, int* out);
+LIGHTGBM_C_EXPORT int LGBM_DevicePredictorFree(DevicePredictorHandle handle);
 // SHAP values on the device from a dense row-major matrix (Booster.predict_contrib_device):
 // nrow x trees-per-iteration x (features + 1) doubles, the layout and length of PREDICT_CONTRIB
 // (LGBM_BoosterCalcNumPredict). `data` and `out_result` may each be host memory or memory of the

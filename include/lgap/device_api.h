@@ -188,5 +188,29 @@ struct PredictTransform {
 void PredictDense(const PackedEnsemble& pk, const void* data, bool f64, int nrow, int ncol, int mode,
                   const PredictTransform* transform, bool data_on_device, bool out_on_device, double* out);
 
+// A packed ensemble kept on the device for repeated prediction (Booster.device_predictor). The
+// constructor uploads `pk` and its batch plan once; Predict takes PredictDense's arguments and
+// gives its results. The object owns one non-blocking stream, device input / output buffers, the
+// [tree][row] scratch of the tree-parallel kernels and, with `pinned`, pinned host staging
+// buffers; all of them only grow, so a call whose shapes have been seen allocates nothing.
+// Batches of at most tree_parallel_rows rows (0: none, at most 65,536) run k_predict_pairs and
+// k_predict_fold, larger ones the row-parallel kernels. Calls are not serialised here.
+enum PredictPath : int { kPathNone = -1, kPathRow = 0, kPathTree = 1 };
+class ResidentEnsemble {
+ public:
+  ResidentEnsemble(const PackedEnsemble& pk, int tree_parallel_rows, bool pinned);
+  ~ResidentEnsemble();
+  ResidentEnsemble(const ResidentEnsemble&) = delete;
+  ResidentEnsemble& operator=(const ResidentEnsemble&) = delete;
+  void Predict(const void* data, bool f64, int nrow, int ncol, int mode, const PredictTransform* transform,
+               bool data_on_device, bool out_on_device, double* out);
+  int last_path() const { return last_path_; }  // the kernel family of the last call that launched
+
+ private:
+  struct Impl;
+  std::unique_ptr<Impl> impl_;
+  int last_path_ = kPathNone;
+};
+
 }  // namespace device
 }  // namespace lgap

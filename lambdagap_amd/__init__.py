@@ -7,8 +7,8 @@ data-parallel across GPUs over RCCL.
 """
 from __future__ import annotations
 
-from .basic import (Booster, Dataset, LightGBMError, Sequence, device_count, device_metric, device_objective,
-                    phase_timer_report, register_logger)
+from .basic import (Booster, Dataset, DevicePredictor, LightGBMError, Sequence, device_count, device_metric,
+                    device_objective, phase_timer_report, register_logger)
 from .callback import EarlyStopException, early_stopping, log_evaluation, record_evaluation, reset_parameter
 from .engine import CVBooster, cv, train
 
@@ -16,8 +16,8 @@ __version__ = "4.6.0.99+mi355x.1"
 
 __all__ = ["Dataset", "Booster", "CVBooster", "Sequence", "LightGBMError", "register_logger", "train", "cv",
            "early_stopping", "log_evaluation", "record_evaluation", "reset_parameter", "EarlyStopException",
-           "device_count", "device_objective", "device_metric", "phase_timer_report", "LGBMModel", "LGBMRegressor",
-           "LGBMClassifier", "LGBMRanker",
+           "device_count", "device_objective", "device_metric", "phase_timer_report", "DevicePredictor", "LGBMModel",
+           "LGBMRegressor", "LGBMClassifier", "LGBMRanker",
            "plot_importance", "plot_split_value_histogram", "plot_metric", "plot_tree", "create_tree_digraph"]
 
 try:

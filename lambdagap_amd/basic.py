@@ -1568,6 +1568,11 @@ class Booster:
             return out_t
         return out_t.reshape(nrow, per)
 
+    def device_predictor(self, start_iteration: int = 0, num_iteration: Optional[int] = None,
+                         tree_parallel_rows: Optional[int] = None, **kwargs: Any) -> "DevicePredictor":
+        """A predictor that keeps the selected iterations packed on the GPU (see ``DevicePredictor``)."""
+        return DevicePredictor(self, start_iteration, num_iteration, tree_parallel_rows, **kwargs)
+
     def predict_contrib_device(self, data: Any, start_iteration: int = 0, num_iteration: Optional[int] = None,
                                **kwargs: Any) -> Any:
         """SHAP values (``predict(data, pred_contrib=True)``) computed on the GPU.
@@ -1895,6 +1900,115 @@ class Booster:
         for t in model["tree_info"]:
             walk(t["tree_structure"], t["tree_index"], 1, None)
         return pd.DataFrame(rows)
+
+
+class DevicePredictor:
+    """A trained model kept packed on the GPU for repeated prediction (``Booster.device_predictor``).
+
+    Creation packs and uploads the iterations ``predict_device`` would select and parses the
+    prediction parameters, once; ``predict`` then only moves rows and launches kernels. The
+    predictor is a snapshot: training the booster further, ``rollback_one_iter``,
+    ``set_leaf_output`` or ``refit`` do not change its output. It keeps its Booster alive (the
+    objective's output transform is the booster's).
+
+    ``predict`` takes what ``predict_device`` takes and returns what it returns: raw scores and
+    leaf indices equal ``Booster.predict`` bit for bit, the transformed output too for numpy input;
+    for a GPU tensor the transform runs on the device. Batches of at most ``tree_parallel_rows``
+    rows run the tree-parallel kernels (one work item per row and tree), larger ones the
+    row-parallel kernels of ``predict_device``; ``last_path`` names the family that served the
+    last call. ``None`` is the measured default, ``0`` never uses the tree-parallel kernels.
+    """
+
+    MAX_TREE_PARALLEL_ROWS = 65536
+    _PATHS = {0: "row", 1: "tree"}
+
+    def __init__(self, booster: Booster, start_iteration: int = 0, num_iteration: Optional[int] = None,
+                 tree_parallel_rows: Optional[int] = None, **kwargs: Any):
+        self.handle = None
+        if tree_parallel_rows is None:
+            tpr = -1
+        else:
+            tpr = int(tree_parallel_rows)
+            if tpr < 0 or tpr > self.MAX_TREE_PARALLEL_ROWS:
+                raise ValueError(f"tree_parallel_rows must be between 0 and {self.MAX_TREE_PARALLEL_ROWS}, "
+                                 f"got {tree_parallel_rows}")
+        if kwargs.pop("pred_contrib", False):
+            raise LightGBMError("predict_device does not support pred_contrib (SHAP values); use Booster.predict or "
+                                "Booster.predict_contrib_device")
+        if num_iteration is None:
+            num_iteration = booster.best_iteration if booster.best_iteration > 0 else -1
+        self.booster = booster
+        handle = ctypes.c_void_p()
+        _check(_LIB.LGBM_BoosterDevicePredictorCreate(
+            booster.handle, ctypes.c_int(start_iteration), ctypes.c_int(num_iteration), ctypes.c_int(tpr),
+            _c_str(param_dict_to_str(kwargs)), ctypes.byref(handle)))
+        self.handle = handle
+        # values per row of the packed slice, fixed like the slice itself
+        self._per_row = {}
+        for ptype in (C_API_PREDICT_NORMAL, C_API_PREDICT_RAW_SCORE, C_API_PREDICT_LEAF_INDEX):
+            n = ctypes.c_int64(0)
+            _check(_LIB.LGBM_BoosterCalcNumPredict(booster.handle, ctypes.c_int(1), ctypes.c_int(ptype),
+                                                   ctypes.c_int(start_iteration), ctypes.c_int(num_iteration),
+                                                   ctypes.byref(n)))
+            self._per_row[ptype] = n.value
+
+    def predict(self, data: Any, raw_score: bool = False, pred_leaf: bool = False) -> Any:
+        if self.handle is None:
+            raise LightGBMError("device_predictor: predict called after free()")
+        ptype = C_API_PREDICT_NORMAL
+        if raw_score:
+            ptype = C_API_PREDICT_RAW_SCORE
+        if pred_leaf:
+            ptype = C_API_PREDICT_LEAF_INDEX
+        tensor, data_ptr, dtype, nrow, ncol, _keep = Booster._device_matrix(data, "device_predictor")
+        per = self._per_row[ptype]
+        out_len = ctypes.c_int64(0)
+        if tensor is None:
+            out = np.empty(nrow * per, dtype=np.float64)
+            _check(_LIB.LGBM_DevicePredictorPredict(
+                self.handle, data_ptr, ctypes.c_int(dtype), ctypes.c_int32(nrow), ctypes.c_int32(ncol),
+                ctypes.c_int(ptype), ctypes.c_int(0), ctypes.c_int(0), ctypes.byref(out_len),
+                out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+            return self.booster._shape_pred(out, nrow, ptype)
+        import torch
+
+        with torch.cuda.device(tensor.device):
+            out_t = torch.empty(nrow * per, dtype=torch.float64, device=tensor.device)
+            # the library works on a stream of its own: the tensor's producer must be done
+            torch.cuda.current_stream().synchronize()
+            _check(_LIB.LGBM_DevicePredictorPredict(
+                self.handle, data_ptr, ctypes.c_int(dtype), ctypes.c_int32(nrow), ctypes.c_int32(ncol),
+                ctypes.c_int(ptype), ctypes.c_int(1), ctypes.c_int(1), ctypes.byref(out_len),
+                ctypes.cast(ctypes.c_void_p(out_t.data_ptr()), ctypes.POINTER(ctypes.c_double))))
+        if nrow == 0 or (per == 1 and ptype != C_API_PREDICT_LEAF_INDEX):
+            return out_t
+        return out_t.reshape(nrow, per)
+
+    @property
+    def last_path(self) -> Optional[str]:
+        """"row" or "tree": the kernel family that served the last call (None before the first)."""
+        if self.handle is None:
+            raise LightGBMError("device_predictor: last_path read after free()")
+        out = ctypes.c_int(-1)
+        _check(_LIB.LGBM_DevicePredictorLastPath(self.handle, ctypes.byref(out)))
+        return self._PATHS.get(out.value)
+
+    def free(self) -> None:
+        if self.handle is not None:
+            handle, self.handle = self.handle, None
+            _check(_LIB.LGBM_DevicePredictorFree(handle))
+
+    def __enter__(self) -> "DevicePredictor":
+        return self
+
+    def __exit__(self, *exc: Any) -> None:
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def _dump_pandas_categorical(pc) -> str:

@@ -21,6 +21,7 @@
 
 #include "device/contrib_kernels.h"
 #include "device/contrib_pack.h"
+#include "device/predict_kernels.h"
 #include "device/predict_pack.h"
 #include "device/traverse_pack.h"
 #include "lgap/arrow.h"
@@ -275,11 +276,33 @@ void PredictRows(Booster* b, const RowSource& src, int predict_type, int start_i
   *out_len = static_cast<int64_t>(n) * per_row;
 }
 
+// the objective's ConvertOutput as a device transform (k_predict_convert)
+device::PredictTransform DeviceOutputTransform(const ObjectiveFunction* obj) {
+  device::PredictTransform tf;
+  int output = 0;
+  double sigmoid = 1.0;
+  if (PointwiseOutputTransform(obj, &output, &sigmoid)) {
+    tf.kind = device::kTransformPointwise;
+    tf.output = output;
+    tf.sigmoid = sigmoid;
+  } else if (obj->device_kind() == DeviceGradKind::kSoftmax) {
+    tf.kind = device::kTransformSoftmax;
+  } else if (obj->device_kind() == DeviceGradKind::kOVA) {
+    tf.kind = device::kTransformOVA;
+    tf.sigmoid = obj->sigmoid();
+  } else if (!obj->IsRanking()) {
+    Log::Fatal("predict_device: objective %s has no device output transform; use raw_score=True or Booster.predict",
+               obj->GetName());
+  }
+  return tf;
+}
+
 // ---- prediction over the packed ensemble (device/predict_pack.h): the device kernels, or the
 // same walk in a host loop (on_device = false, the CPU-only test hook)
 void PredictPacked(Booster* b, const void* data, int data_type, int32_t nrow, int32_t ncol, int predict_type,
                    int start_iteration, int num_iteration, const char* parameter, bool on_device,
-                   bool data_on_device, bool out_on_device, int64_t* out_len, double* out) {
+                   bool data_on_device, bool out_on_device, int64_t* out_len, double* out,
+                   bool host_tree_parallel = false) {
   std::shared_lock<std::shared_mutex> lk(b->mu_);
   Config pc = ParseConfig(parameter);
   GBDT* g = b->boosting_.get();
@@ -311,32 +334,100 @@ void PredictPacked(Booster* b, const void* data, int data_type, int32_t nrow, in
   const int mode = leaf ? device::kPredictLeaf : device::kPredictRaw;
   const bool f64 = data_type == C_API_DTYPE_FLOAT64;
   const ObjectiveFunction* obj = g->objective();
-  if (!on_device) {
+  if (!on_device && host_tree_parallel) {
+    device::PredictPackedHostTreeParallel(pk.View(), data, f64, nrow, ncol, mode, out);
+  } else if (!on_device) {
     device::PredictPackedHost(pk.View(), data, f64, nrow, ncol, mode, out);
   } else {
     // the objective's ConvertOutput as a device transform, used only when the output stays there
     device::PredictTransform tf;
-    if (normal && obj != nullptr && out_on_device) {
-      int output = 0;
-      double sigmoid = 1.0;
-      if (PointwiseOutputTransform(obj, &output, &sigmoid)) {
-        tf.kind = device::kTransformPointwise;
-        tf.output = output;
-        tf.sigmoid = sigmoid;
-      } else if (obj->device_kind() == DeviceGradKind::kSoftmax) {
-        tf.kind = device::kTransformSoftmax;
-      } else if (obj->device_kind() == DeviceGradKind::kOVA) {
-        tf.kind = device::kTransformOVA;
-        tf.sigmoid = obj->sigmoid();
-      } else if (!obj->IsRanking()) {
-        Log::Fatal("predict_device: objective %s has no device output transform; use raw_score=True or Booster.predict",
-                   obj->GetName());
-      }
-    }
+    if (normal && obj != nullptr && out_on_device) tf = DeviceOutputTransform(obj);
     device::PredictDense(pk, data, f64, nrow, ncol, mode, &tf, data_on_device, out_on_device, out);
   }
   // host output: the host's own ConvertOutput per row, bit-identical to PredictRows
   if (normal && obj != nullptr && !(on_device && out_on_device)) {
+    std::vector<double> raw(per_row);
+    for (int64_t i = 0; i < nrow; ++i) {
+      double* o = out + i * per_row;
+      std::copy(o, o + per_row, raw.begin());
+      obj->ConvertOutput(raw.data(), o);
+    }
+  }
+  *out_len = static_cast<int64_t>(nrow) * per_row;
+}
+
+// ---- a packed ensemble resident on the device (Booster.device_predictor): PredictPacked's
+// checks and packing done once, as FastConfig does for single rows on the host
+struct DevicePredictor {
+  Booster* booster = nullptr;  // for the objective's output transform; the caller keeps it alive
+  std::mutex mu;               // one call at a time: the buffers and the stream are the handle's
+  std::unique_ptr<device::ResidentEnsemble> ensemble;
+  bool disable_shape_check = false;
+  int num_features = 0;  // MaxFeatureIdx() + 1 at creation
+  int num_trees = 0;     // packed
+  int num_tree_per_iteration = 1;
+};
+
+DevicePredictor* MakeDevicePredictor(Booster* b, int start_iteration, int num_iteration, int tree_parallel_rows,
+                                     const char* parameter) {
+  std::shared_lock<std::shared_mutex> lk(b->mu_);
+  Config pc = ParseConfig(parameter);
+  GBDT* g = b->boosting_.get();
+  if (pc.pred_early_stop) {
+    Log::Fatal("predict_device does not support pred_early_stop; use Booster.predict");
+  }
+  if (device::DeviceCount() <= 0) {
+    Log::Fatal("predict_device: no gfx950 GPU is visible to this process; use Booster.predict for host prediction");
+  }
+  if (tree_parallel_rows < 0) tree_parallel_rows = device::kTreeParallelDefaultRows;
+  g->InitPredict(start_iteration, num_iteration, false);
+  if (g->NumPredictOneRow(start_iteration, num_iteration, false, false) != g->NumModelPerIteration()) {
+    Log::Fatal("predict_device: the objective returns %d values per row from %d trees per iteration; use Booster.predict",
+               g->NumPredictOneRow(start_iteration, num_iteration, false, false), g->NumModelPerIteration());
+  }
+  auto dp = std::make_unique<DevicePredictor>();
+  dp->booster = b;
+  dp->disable_shape_check = pc.predict_disable_shape_check;
+  dp->num_features = g->MaxFeatureIdx() + 1;
+  const device::PackedEnsemble pk = device::PackEnsemble(*g, start_iteration, num_iteration);
+  dp->num_trees = static_cast<int>(pk.trees.size());
+  dp->num_tree_per_iteration = pk.num_tree_per_iteration;
+  dp->ensemble = std::make_unique<device::ResidentEnsemble>(pk, tree_parallel_rows, true);
+  return dp.release();
+}
+
+void DevicePredictorPredict(DevicePredictor* dp, const void* data, int data_type, int32_t nrow, int32_t ncol,
+                            int predict_type, bool data_on_device, bool out_on_device, int64_t* out_len,
+                            double* out) {
+  if (predict_type == C_API_PREDICT_CONTRIB) {
+    Log::Fatal("predict_device does not support pred_contrib (SHAP values); use Booster.predict or "
+               "Booster.predict_contrib_device");
+  }
+  if (predict_type != C_API_PREDICT_NORMAL && predict_type != C_API_PREDICT_RAW_SCORE &&
+      predict_type != C_API_PREDICT_LEAF_INDEX) {
+    Log::Fatal("predict_device: unknown predict_type %d", predict_type);
+  }
+  if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) {
+    Log::Fatal("device_predictor: data_type must be float32 or float64");
+  }
+  const bool leaf = predict_type == C_API_PREDICT_LEAF_INDEX;
+  const bool normal = predict_type == C_API_PREDICT_NORMAL;
+  if (!dp->disable_shape_check && ncol != dp->num_features && ncol > 0) {
+    Log::Fatal("The number of features in data (%d) is not the same as it was in training data (%d).\n"
+               "You can set ``predict_disable_shape_check=true`` to discard this error, but please be aware what you are doing.",
+               ncol, dp->num_features);
+  }
+  const int per_row = leaf ? dp->num_trees : dp->num_tree_per_iteration;
+  std::lock_guard<std::mutex> call(dp->mu);
+  // the objective is the booster's own: read under its lock, like every other prediction
+  std::shared_lock<std::shared_mutex> lk(dp->booster->mu_);
+  const ObjectiveFunction* obj = dp->booster->boosting_->objective();
+  device::PredictTransform tf;
+  if (normal && obj != nullptr && out_on_device) tf = DeviceOutputTransform(obj);
+  dp->ensemble->Predict(data, data_type == C_API_DTYPE_FLOAT64, nrow, ncol,
+                        leaf ? device::kPredictLeaf : device::kPredictRaw, &tf, data_on_device, out_on_device, out);
+  // host output: the host's own ConvertOutput per row, bit-identical to PredictRows
+  if (normal && obj != nullptr && !out_on_device) {
     std::vector<double> raw(per_row);
     for (int64_t i = 0; i < nrow; ++i) {
       double* o = out + i * per_row;
@@ -1230,6 +1321,45 @@ int LGBM_BoosterTestPackedPredict(BoosterHandle handle, const void* data, int da
   API_BEGIN();
   PredictPacked(B(handle), data, data_type, nrow, ncol, predict_type, start_iteration, num_iteration, parameter, false,
                 false, false, out_len, out_result);
+  API_END();
+}
+
+int LGBM_BoosterTestPackedPredictTreeParallel(BoosterHandle handle, const void* data, int data_type, int32_t nrow,
+                                              int32_t ncol, int predict_type, int start_iteration, int num_iteration,
+                                              const char* parameter, int64_t* out_len, double* out_result) {
+  API_BEGIN();
+  PredictPacked(B(handle), data, data_type, nrow, ncol, predict_type, start_iteration, num_iteration, parameter, false,
+                false, false, out_len, out_result, true);
+  API_END();
+}
+
+int LGBM_BoosterDevicePredictorCreate(BoosterHandle handle, int start_iteration, int num_iteration,
+                                      int tree_parallel_rows, const char* parameter, DevicePredictorHandle* out) {
+  API_BEGIN();
+  *out = MakeDevicePredictor(B(handle), start_iteration, num_iteration, tree_parallel_rows, parameter);
+  API_END();
+}
+
+int LGBM_DevicePredictorPredict(DevicePredictorHandle handle, const void* data, int data_type, int32_t nrow,
+                                int32_t ncol, int predict_type, int data_on_device, int out_on_device,
+                                int64_t* out_len, double* out_result) {
+  API_BEGIN();
+  DevicePredictorPredict(static_cast<DevicePredictor*>(handle), data, data_type, nrow, ncol, predict_type,
+                         data_on_device != 0, out_on_device != 0, out_len, out_result);
+  API_END();
+}
+
+int LGBM_DevicePredictorLastPath(DevicePredictorHandle handle, int* out) {
+  API_BEGIN();
+  auto* dp = static_cast<DevicePredictor*>(handle);
+  std::lock_guard<std::mutex> call(dp->mu);
+  *out = dp->ensemble->last_path();
+  API_END();
+}
+
+int LGBM_DevicePredictorFree(DevicePredictorHandle handle) {
+  API_BEGIN();
+  delete static_cast<DevicePredictor*>(handle);
   API_END();
 }
 

@@ -43,5 +43,25 @@ struct PredictShape {
 // leaf: k_predict_leaf (no accumulators); elem: bytes of one feature value
 PredictShape PlanPredictShape(int ncol, size_t elem, int num_tree_per_iteration, bool leaf);
 
+// ---- the tree-parallel path of the resident predictor (k_predict_pairs, then k_predict_fold):
+// a block owns one PredictBatch and a tile of rows, its lanes spread over the (row, tree) pairs.
+constexpr int kPairSmallTileRows = 64;            // the row tile of batches up to kPairSmallTileMaxRows
+constexpr int kPairLargeTileRows = 256;           // and of larger ones: each staged run serves more rows
+constexpr int kPairSmallTileMaxRows = 1024;
+constexpr int kPairRowLdsBytes = 32 * 1024;       // a tile's rows are staged in LDS up to this size
+constexpr int kTreeParallelMaxRows = 65536;       // bounds the [tree][row] scratch
+// Batches of at most this many rows take the tree-parallel path unless the caller says otherwise.
+// Measured (profiles/device_predictor.md): faster than the row-parallel kernels at every row
+// count of the grid up to the limit.
+constexpr int kTreeParallelDefaultRows = kTreeParallelMaxRows;
+
+struct PairShape {
+  int tile_rows;     // rows per block
+  int stage_rows;    // the tile's rows are staged in LDS
+  size_t lds_bytes;  // dynamic LDS of the launch
+  long long grid;    // row tiles x batches, one block each
+};
+PairShape PlanPairShape(int nrow, int ncol, size_t elem, int num_batches);
+
 }  // namespace device
 }  // namespace lgap

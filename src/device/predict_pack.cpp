@@ -2,6 +2,7 @@
 #include "device/predict_pack.h"
 
 #include <algorithm>
+#include <cstring>
 
 #include "lgap/boosting.h"
 #include "lgap/log.h"
@@ -99,7 +100,56 @@ void HostLoop(const PackedView& v, const T* data, int64_t nrow, int ncol, int mo
   }
 }
 
+template <typename T>
+void HostPairsFold(const PackedView& v, const T* data, int64_t nrow, int ncol, int mode, double* out) {
+  const int K = v.num_tree_per_iteration;
+  const int64_t pairs = nrow * v.num_trees;
+  if (mode == kPredictLeaf) {
+#pragma omp parallel for schedule(static)
+    for (int64_t p = 0; p < pairs; ++p) {
+      const int64_t t = p / nrow, i = p % nrow;
+      const PTree tr = v.trees[t];
+      out[i * v.num_trees + t] = PredLeaf(v.nodes + tr.node_off, tr.num_leaves, v.cat_boundaries + tr.cat_off,
+                                          v.cat_threshold, data + i * ncol, ncol);
+    }
+    return;
+  }
+  std::vector<double> vals(static_cast<size_t>(pairs));
+#pragma omp parallel for schedule(static)
+  for (int64_t p = 0; p < pairs; ++p) {
+    const int64_t t = p / nrow, i = p % nrow;
+    const PTree tr = v.trees[t];
+    vals[p] = PredPairValue(v, tr, v.nodes + tr.node_off, v.leaf_value + tr.leaf_off, data + i * ncol, ncol);
+  }
+#pragma omp parallel for schedule(static)
+  for (int64_t q = 0; q < nrow * K; ++q) {
+    const int64_t k = q / nrow, i = q % nrow;
+    out[i * K + k] = PredFoldRow(v, vals.data(), nrow, i, static_cast<int>(k));
+  }
+}
+
 }  // namespace
+
+void PredictPackedHostTreeParallel(const PackedView& view, const void* data, bool f64, int64_t nrow, int ncol,
+                                   int mode, double* out) {
+  if (nrow <= 0) return;
+  if (f64) HostPairsFold(view, static_cast<const double*>(data), nrow, ncol, mode, out);
+  else HostPairsFold(view, static_cast<const float*>(data), nrow, ncol, mode, out);
+}
+
+void CopyHostBytes(void* dst, const void* src, size_t bytes) {
+  constexpr size_t kBlock = size_t(1) << 20;
+  if (bytes <= 4 * kBlock) {
+    std::memcpy(dst, src, bytes);
+    return;
+  }
+  const int64_t blocks = static_cast<int64_t>((bytes + kBlock - 1) / kBlock);
+#pragma omp parallel for schedule(static)
+  for (int64_t b = 0; b < blocks; ++b) {
+    const size_t off = static_cast<size_t>(b) * kBlock;
+    std::memcpy(static_cast<char*>(dst) + off, static_cast<const char*>(src) + off, std::min(kBlock, bytes - off));
+  }
+}
 
 void PredictPackedHost(const PackedView& view, const void* data, bool f64, int64_t nrow, int ncol, int mode,
                        double* out) {

@@ -10,6 +10,7 @@
 #pragma once
 
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -106,6 +107,13 @@ enum PredictMode : int { kPredictRaw = 0, kPredictLeaf = 1 };
 // rows x PredictWidth(view, mode) doubles in out, by the shared walk in a host loop
 void PredictPackedHost(const PackedView& view, const void* data, bool f64, int64_t nrow, int ncol, int mode,
                        double* out);
+// the same result by the tree-parallel algorithm of k_predict_pairs / k_predict_fold in host
+// loops: every (row, tree) pair into a [tree][row] array, then the shared fold
+void PredictPackedHostTreeParallel(const PackedView& view, const void* data, bool f64, int64_t nrow, int ncol,
+                                   int mode, double* out);
+
+// memcpy, split over the OpenMP threads above a few MiB (the resident predictor's staging copies)
+void CopyHostBytes(void* dst, const void* src, size_t bytes);
 
 inline int PredictWidth(const PackedView& v, int mode) {
   return mode == kPredictLeaf ? v.num_trees : v.num_tree_per_iteration;
@@ -183,6 +191,28 @@ LGAP_HD inline double PredLeafOutput(const PackedView& v, const PTree& tr, int l
     out = out + prod;
   }
   return out;
+}
+
+// ---- the tree-parallel form: one walk per (row, tree) pair, then a fold per (row, class) ----
+
+// Tree `tree`'s value for one row: what the row-parallel walk adds to the row's accumulator
+template <typename T>
+LGAP_HD inline double PredPairValue(const PackedView& v, const PTree& tr, const PNode* nodes, const double* leaves,
+                                    const T* row, int ncol) {
+  const int leaf = PredLeaf(nodes, tr.num_leaves, v.cat_boundaries + tr.cat_off, v.cat_threshold, row, ncol);
+  return PredLeafOutput(v, tr, leaf, leaves[leaf], row, ncol);
+}
+
+// Class k's raw score of row `row` from vals[tree][row] (rows `stride` apart): from 0.0, the
+// trees k, k + K, ... added in ascending order, then average_output's division. The host's
+// out[k] += Predict(x) order from the same starting value: the same bits.
+LGAP_HD inline double PredFoldRow(const PackedView& v, const double* vals, int64_t stride, int64_t row, int k) {
+  double acc = 0.0;
+  for (int tree = k; tree < v.num_trees; tree += v.num_tree_per_iteration) {
+    acc = acc + vals[static_cast<int64_t>(tree) * stride + row];
+  }
+  if (v.average_output && v.num_iterations > 0) acc /= v.num_iterations;
+  return acc;
 }
 
 }  // namespace device
